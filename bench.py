@@ -13,6 +13,13 @@ HBM, nothing shared) for quick experiments. See DESIGN.md.
 
 Launch: `python bench.py` (N=1) or `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N`. Prints ONE JSON line on rank 0.
+
+A plain run generates the batch, loads it, warms up, times `--steps` replays and prints the result
+line (value, ms_per_step, the roofline fields that follow from the engine's own counters). `--full`
+adds everything else: the per-document state digests and their comparison with the oracle, the CPU
+and JS baselines, the bulk summaries and catch-up blobs, the fixture checks of `ob` / `local`, and
+T2's oracle sample and summary gather. `--dump-outputs DIR` writes what the last timed replay left
+(see _dump_outputs) as DIR/<name>.npy for output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -107,7 +114,16 @@ def main():
                     help="initialise torch.distributed (nccl = RCCL) even at one rank, so the gathers go over RCCL")
     ap.add_argument("--no-js-baseline", action="store_true", help="skip the JS worker_threads baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline pool (0 = every usable host core)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the checks and secondary measurements: state digests and "
+                         "their comparison with the oracle, CPU and JS baselines, bulk summaries and catch-up blobs, "
+                         "fixture checks (ob, local), T2's oracle sample and summary gather, T3's summary emission")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float32/float64, < 64 MB; a "
+                         "fixed seeded sample where the whole output is larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -230,10 +246,23 @@ def main():
     rec["kernel_ms"] = sum(kernel_ms) / len(kernel_ms)
     digests = None
     t2_check = None
+    dump_dir = args.dump_outputs
+    if dump_dir and world > 1:  # (every rank writes its own shard's results)
+        dump_dir = os.path.join(dump_dir, f"rank{rank}")
     if mt:
         hdrs = eng.mt_headers()
         rec["status_bad"] = int((hdrs["status"] != 0).sum())
         rec["checksum"] = shard.state_checksum(hdrs, doc_base)
+        if dump_dir:
+            _dump_mt_outputs(eng, hdrs, dump_dir)
+    elif args.full or dump_dir:
+        got = eng.map_fetch_sparse() if args.sparse else eng.map_fetch()
+        if dump_dir:
+            _dump_map_outputs(got, args.sparse, dump_dir)
+        if args.full:
+            rec["checksum"] = shard.map_sparse_checksum(*got, doc_base) if args.sparse else shard.map_checksum(got, doc_base)
+        del got
+    if mt and args.full:
         # every document's content digest (fmt_mt_state_digest: leaves, props by value, text, header)
         t = time.perf_counter()
         digests = eng.mt_digests()
@@ -244,10 +273,6 @@ def main():
             _check_local_farms(eng, hdrs, fixtures, docs)
         if t2 and args.t2_check_docs > 0:
             t2_check = _t2_oracle_check(batch, digests, docs, doc_base, args.t2_check_docs, world)
-    elif args.sparse:
-        rec["checksum"] = shard.map_sparse_checksum(*eng.map_fetch_sparse(), doc_base)
-    else:
-        rec["checksum"] = shard.map_checksum(eng.map_fetch(), doc_base)
     stats = shard.gather_stats(rec, dist, device="cuda") if dist is not None else rec
     content = None
     if digests is not None:  # whole-job content digest: Σ over ranks of Σ_d mix(global d, digest_d)
@@ -258,7 +283,7 @@ def main():
             n_bad = shard.gather_u64(t2_check["mismatches"], dist, device="cuda") if dist is not None else [t2_check["mismatches"]]
             t2_check = {**t2_check, "docs_all_ranks": sum(n_chk), "mismatches_all_ranks": sum(n_bad)}
     gathered = None
-    if t2 and args.gather_docs > 0:
+    if t2 and args.full and args.gather_docs > 0:
         from fluidframework_amd.summary import legacy_summary
 
         t = time.perf_counter()
@@ -277,7 +302,7 @@ def main():
                         "what": f"legacy summaries (header, body) of the first {args.gather_docs} documents of every "
                                 "shard, gathered to rank 0 (all-gather of byte counts + grouped send/recv)"}
     summaries = None
-    if mt and not t2 and not ob and not loc and not args.no_summaries:
+    if args.full and mt and not t2 and not ob and not loc and not args.no_summaries:
         # every document's legacy summary from the converged state (device merge + host JSON on the
         # usable cores), timed apart from the replay; a sample checked against the Python host
         from fluidframework_amd.summary import legacy_summary
@@ -307,7 +332,7 @@ def main():
     achieved = bytes_per_launch / (avg_kernel_ms / 1e3) / 1e9
 
     cpu = cpu_js = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not t2:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not t2:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle  # CPU baseline only ("port" of the reference path)
 
@@ -450,7 +475,9 @@ def main():
             "cpu_baseline": cpu,
             # secondary: the plain-JS observer restatement on worker_threads
             **({"cpu_baseline_js": cpu_js} if cpu_js is not None else {}),
-            "state_checksum": f"{shard.combine_checksums(stats):016x}",
+            "full": args.full,
+            # (map: the checksum is over the fetched result tables, a --full step)
+            "state_checksum": f"{shard.combine_checksums(stats):016x}" if mt or args.full else None,
             "content_digest": f"{sum(content) & 0xFFFFFFFFFFFFFFFF:016x}" if content is not None else None,
             "checked_vs_oracle_docs": (cpu or {}).get("checked_vs_oracle_docs", 0) + (
                 t2_check["docs_all_ranks"] if t2_check else 0),
@@ -465,6 +492,117 @@ def main():
     eng.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20240229             # the samples below are the same rows in every run
+DUMP_HEADER_DOCS = 100_000      # result headers written (12 x 8 B each)
+DUMP_SAMPLE_BYTES = 40 << 20     # full states / table rows written beside them (whole dump < 64 MB)
+
+
+def _columns(rec):
+    """A structured array as a float64 matrix, one column per scalar (a sub-array field gives one
+    column per element). Every field is an integer; 64-bit ones are split into their low and high
+    32-bit words, so each value is exact in float64."""
+    import numpy as np
+
+    cols = []
+    for name in rec.dtype.names:
+        a = rec[name].reshape(len(rec), int(np.prod(rec[name].shape[1:])))
+        if a.dtype.itemsize == 8:
+            a = a.astype(np.uint64)
+            cols += [(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)]
+        else:
+            cols.append(a.astype(np.float64))
+    return np.concatenate(cols, axis=1)
+
+
+def _sample_rows(n, k):
+    """min(n, k) of the rows 0..n-1, ascending: the same rows for the same (n, k)."""
+    import numpy as np
+
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).permutation(n)[:k]).astype(np.int64)
+
+
+def _dump_mt_outputs(eng, hdrs, dirname):
+    """--dump-outputs of a merge-tree replay: what a caller of fmt_mt_run fetches afterwards.
+    headers.npy: the result headers (DOC_RESULT_DTYPE columns) of the documents header_docs.npy (all of
+    them up to DUMP_HEADER_DOCS, else a seeded sample). sample_docs.npy: seeded documents whose whole
+    state follows, concatenated in that order (each document's share is its header's n_leaves /
+    n_chars / n_props): sample_leaves.npy (LEAF_DTYPE columns, rm_clients as two words),
+    sample_chars.npy (UTF-16 units, float32), sample_props.npy (n + the 8 kv entries). A document
+    larger than the sample budget (T3's one document) is written as seeded rows of its arrays, with
+    the row numbers in sample_leaf_rows.npy / sample_char_rows.npy."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    docs = len(hdrs)
+
+    def save(name, a, dtype=np.float64):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    hrows = _sample_rows(docs, DUMP_HEADER_DOCS)
+    save("header_docs", hrows)
+    save("headers", _columns(hdrs[hrows]))
+    cost = 80 * hdrs["n_leaves"].astype(np.int64) + 4 * hdrs["n_chars"].astype(np.int64) + 72 * hdrs["n_props"].astype(np.int64)
+    if docs == 1 and int(cost[0]) > DUMP_SAMPLE_BYTES:
+        lv, ch, pr = eng.mt_doc(0, hdrs[0])
+        lrows = _sample_rows(len(lv), DUMP_SAMPLE_BYTES // 2 // 80)
+        crows = _sample_rows(len(ch), DUMP_SAMPLE_BYTES // 4 // 4)
+        save("sample_docs", [0])
+        save("sample_leaf_rows", lrows)
+        save("sample_char_rows", crows)
+        save("sample_leaves", _columns(lv[lrows]))
+        save("sample_chars", ch[crows], np.float32)
+        save("sample_props", _columns(pr[: DUMP_SAMPLE_BYTES // 4 // 72]))
+        return
+    order = np.random.default_rng(DUMP_SEED).permutation(docs)[:4096]
+    order = order[hdrs["status"][order] == 0]
+    n = int(np.searchsorted(np.cumsum(cost[order]), DUMP_SAMPLE_BYTES, side="right"))
+    sample = np.sort(order[:n])
+    leaves, chars, props = [], [], []
+    for d in sample:
+        lv, ch, pr = eng.mt_doc(int(d), hdrs[d])
+        leaves.append(_columns(lv))
+        chars.append(ch)
+        props.append(_columns(pr))
+    save("sample_docs", sample)
+    save("sample_leaves", np.concatenate(leaves) if leaves else np.zeros((0, 10)))
+    save("sample_chars", np.concatenate(chars) if chars else np.zeros(0), np.float32)
+    save("sample_props", np.concatenate(props) if props else np.zeros((0, 9)))
+
+
+def _dump_map_outputs(got, sparse, dirname):
+    """--dump-outputs of a SharedMap replay. Dense (fmt_map_fetch): slots.npy = the (value,
+    birth_seq) slot rows of the seeded documents slot_docs.npy, shape (k, key_bound, 2). Sparse
+    (fmt_map_fetch_sparse): counts.npy = every document's live-key count (a seeded sample above
+    DUMP_HEADER_DOCS documents, count_docs.npy), entries.npy = the (key, value, birth_seq) entries of
+    the seeded documents entry_docs.npy, concatenated in that order."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if not sparse:
+        docs, key_bound = got.shape
+        rows = _sample_rows(docs, max(1, DUMP_SAMPLE_BYTES // (16 * key_bound)))
+        save("slot_docs", rows)
+        save("slots", _columns(got[rows].reshape(-1)).reshape(len(rows), key_bound, 2))
+        return
+    counts, entries = got
+    crows = _sample_rows(len(counts), DUMP_HEADER_DOCS)
+    save("count_docs", crows)
+    save("counts", counts[crows])
+    first = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+    order = np.random.default_rng(DUMP_SEED).permutation(len(counts))[:100_000]
+    n = int(np.searchsorted(np.cumsum(counts[order].astype(np.int64)) * 24, DUMP_SAMPLE_BYTES, side="right"))
+    sample = np.sort(order[:n])
+    save("entry_docs", sample)
+    parts = [_columns(entries[int(first[d]):int(first[d + 1])]) for d in sample]
+    save("entries", np.concatenate(parts) if parts else np.zeros((0, 3)))
 
 
 def _t2_oracle_check(batch, digests, docs, doc_base, n_check, world):
@@ -760,34 +898,38 @@ def bench_t3(args, rank, world, local_rank, dist):
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
     prof = eng.huge_profile(0)
     log(rank, f"[bench] t3 phase clocks per op: " + ", ".join(f"{k} {v / n_ops:.0f}" for k, v in prof.items()))
-    # Summary emission of the replayed document (SharedString.summarizeCore, legacy format:
-    # snapshotlegacy.ts:126-193 + the catchupOps blob, sequence.ts:949-964), timed on its own:
-    # the device merge of the segment runs, host JSON, the catch-up ranges' fetch and their messages.
-    import hashlib
+    if args.dump_outputs:
+        _dump_mt_outputs(eng, hdrs, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))
+    t3_summary = None
+    if args.full or args.t3_check:
+        # Summary emission of the replayed document (SharedString.summarizeCore, legacy format:
+        # snapshotlegacy.ts:126-193 + the catchupOps blob, sequence.ts:949-964), timed on its own:
+        # the device merge of the segment runs, host JSON, the catch-up ranges' fetch and their messages.
+        import hashlib
 
-    from fluidframework_amd import summary as fsum
-    from fluidframework_amd.streams import op_messages
+        from fluidframework_amd import summary as fsum
+        from fluidframework_amd.streams import op_messages
 
-    names = batch.clients[0] if batch.clients else [f"client-{k}" for k in range(64)]
-    min_seq = int(hdrs[0]["min_seq"])
-    t = time.perf_counter()
-    stiming = eng.mt_summarize_legacy(batch.keys, batch.values)
-    head, body = eng.mt_summary(0)
-    cu = eng.mt_catchup(0, hdrs[0])
-    msgs = op_messages(batch, 0, min_seq, names)
-    cblob = fsum.catchup_blob(fsum.catchup_messages(msgs, cu, min_seq))
-    sum_s = time.perf_counter() - t
-    blob_hash = hashlib.sha256("\x00".join([head, body or "", cblob or ""]).encode("utf-8")).hexdigest()[:16]
-    t3_summary = {"seconds": sum_s, "kernel_ms": stiming["kernel_ms"], "fetch_ms": stiming["fetch_ms"],
-                  "format_ms": stiming["format_ms"], "header_bytes": len(head), "body_bytes": len(body or ""),
-                  "catchup_bytes": len(cblob or ""), "catchup_ops": int(((batch.ops["flags"] & MT_F_CATCHUP) != 0).sum()),
-                  "catchup_ranges": int(len(cu)), "sha16": blob_hash,
-                  "what": "legacy summary (header + body at minSeq, snapshotlegacy.ts:126-193) + catchupOps "
-                          "(sequence.ts:949-1018) of the 10M-segment document, after the timed replay"}
-    log(rank, f"[bench] t3 summary: {sum_s:.2f}s, header {len(head)} B, body {len(body or '')} B, "
-              f"catchup {len(cblob or '')} B ({len(cu)} ranges), sha {blob_hash}")
+        names = batch.clients[0] if batch.clients else [f"client-{k}" for k in range(64)]
+        min_seq = int(hdrs[0]["min_seq"])
+        t = time.perf_counter()
+        stiming = eng.mt_summarize_legacy(batch.keys, batch.values)
+        head, body = eng.mt_summary(0)
+        cu = eng.mt_catchup(0, hdrs[0])
+        msgs = op_messages(batch, 0, min_seq, names)
+        cblob = fsum.catchup_blob(fsum.catchup_messages(msgs, cu, min_seq))
+        sum_s = time.perf_counter() - t
+        blob_hash = hashlib.sha256("\x00".join([head, body or "", cblob or ""]).encode("utf-8")).hexdigest()[:16]
+        t3_summary = {"seconds": sum_s, "kernel_ms": stiming["kernel_ms"], "fetch_ms": stiming["fetch_ms"],
+                      "format_ms": stiming["format_ms"], "header_bytes": len(head), "body_bytes": len(body or ""),
+                      "catchup_bytes": len(cblob or ""), "catchup_ops": int(((batch.ops["flags"] & MT_F_CATCHUP) != 0).sum()),
+                      "catchup_ranges": int(len(cu)), "sha16": blob_hash,
+                      "what": "legacy summary (header + body at minSeq, snapshotlegacy.ts:126-193) + catchupOps "
+                              "(sequence.ts:949-1018) of the 10M-segment document, after the timed replay"}
+        log(rank, f"[bench] t3 summary: {sum_s:.2f}s, header {len(head)} B, body {len(body or '')} B, "
+                  f"catchup {len(cblob or '')} B ({len(cu)} ranges), sha {blob_hash}")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle  # CPU baseline only ("port" of the reference path, with its length index)
 
@@ -861,6 +1003,7 @@ def bench_t3(args, rank, world, local_rank, dist):
                                     "a group scan, one slot list and one leaf block (HBM/L2 round trips), plus "
                                     "block/heap updates; bandwidth is idle by construction",
                          "bytes_per_launch": bytes_per_launch, "avg_kernel_ms": avg_kernel_ms},
+            "full": args.full,
             "cpu_baseline": cpu,
             "t3_oracle_check": t3_check,
             "t3_summary": t3_summary,

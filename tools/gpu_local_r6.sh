@@ -12,7 +12,7 @@ step() { echo "[$(date +%T)] $1" >> $OUT/progress.txt; }
 timeout -k 10 600 python3 -u -m pytest tests/test_local_client.py tests/test_local_spec.py -m gpu -x -v \
     --timeout 240 --timeout-method thread -p no:cacheprovider > $OUT/pytest_local.log 2>&1 && step pytest \
  && OUT=$OUT WORKLOAD=local LIMIT=400 bash tools/gpu_ab_run.sh locCL locSL locCSL && step ab \
- && timeout -k 10 500 python3 -u bench.py --workload local --steps 3 --warmup 1 --cpu-seconds 20 > $OUT/bench_local_100k.log 2>&1 && step bench100k \
+ && timeout -k 10 500 python3 -u bench.py --full --workload local --steps 3 --warmup 1 --cpu-seconds 20 > $OUT/bench_local_100k.log 2>&1 && step bench100k \
  && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_local -o run -- \
       python3 bench.py --workload local --steps 2 --warmup 1 --no-cpu-baseline > $OUT/trace_local.log 2>&1 && step trace \
  && timeout -k 10 600 python3 -u -m pytest tests/test_gpu_huge.py tests/test_huge_checkpoint.py tests/test_obliterate_ceiling.py tests/test_writer_ceiling.py -m gpu -x -v \

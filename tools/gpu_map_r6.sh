@@ -10,12 +10,12 @@ mkdir -p $OUT
 step() { echo "[$(date +%T)] $1" >> $OUT/progress.txt; }
 D="python3 bench.py --workload map --no-cpu-baseline"
 S="python3 bench.py --workload map --sparse --key-pool 1048576 --no-cpu-baseline"
-timeout -k 10 400 python3 -u bench.py --workload map --steps 10 --warmup 2 > $OUT/bench_M2.log 2>&1 && step bench_M2 \
+timeout -k 10 400 python3 -u bench.py --full --workload map --steps 10 --warmup 2 > $OUT/bench_M2.log 2>&1 && step bench_M2 \
  && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_M2 -o run -- $D --steps 5 --warmup 1 > $OUT/trace_M2.log 2>&1 && step trace_M2 \
  && timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_M2 -o run -- $D --steps 1 --warmup 0 > $OUT/pmc_fetch_M2.log 2>&1 && step fetch_M2 \
  && timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_M2 -o run -- $D --steps 1 --warmup 0 > $OUT/pmc_write_M2.log 2>&1 && step write_M2 \
  && timeout -s KILL 150 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_lds_M2 -o run -- $D --steps 1 --warmup 0 > $OUT/pmc_lds_M2.log 2>&1 && step lds_M2 \
- && timeout -k 10 400 python3 -u bench.py --workload map --sparse --key-pool 1048576 --steps 10 --warmup 2 > $OUT/bench_M2_sparse.log 2>&1 && step bench_sparse \
+ && timeout -k 10 400 python3 -u bench.py --full --workload map --sparse --key-pool 1048576 --steps 10 --warmup 2 > $OUT/bench_M2_sparse.log 2>&1 && step bench_sparse \
  && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_M2_sparse -o run -- $S --steps 5 --warmup 1 > $OUT/trace_M2_sparse.log 2>&1 && step trace_sparse \
  && timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_sparse -o run -- $S --steps 1 --warmup 0 > $OUT/pmc_fetch_sparse.log 2>&1 && step fetch_sparse \
  && timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_sparse -o run -- $S --steps 1 --warmup 0 > $OUT/pmc_write_sparse.log 2>&1 && step write_sparse \

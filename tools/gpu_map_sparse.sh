@@ -10,7 +10,7 @@ B="python3 bench.py --workload map --sparse --key-pool 1048576 --no-cpu-baseline
 step() { echo "[$(date +%T)] $1" >> $OUT/progress.txt; }
 timeout -k 10 300 python3 -u -m pytest tests/test_gpu_parity.py -x -v -k "sparse" --timeout 240 --timeout-method thread -p no:cacheprovider > $OUT/pytest_map_sparse.log 2>&1 \
  && step pytest \
- && timeout -k 10 400 python3 -u bench.py --workload map --sparse --key-pool 1048576 --steps 5 > $OUT/bench_M2_sparse.log 2>&1 \
+ && timeout -k 10 400 python3 -u bench.py --full --workload map --sparse --key-pool 1048576 --steps 5 > $OUT/bench_M2_sparse.log 2>&1 \
  && step bench \
  && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_M2_sparse -o run -- $B --steps 2 --warmup 1 > $OUT/trace.log 2>&1 \
  && step trace \

@@ -7,8 +7,8 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof
 mkdir -p $OUT
 B="python3 bench.py --no-cpu-baseline"
-timeout -k 10 600 python3 bench.py --steps 3 --warmup 1 > $OUT/bench_T1.log 2>&1 \
- && timeout -k 10 600 python3 bench.py --workload map --steps 5 --warmup 1 > $OUT/bench_M2.log 2>&1 \
+timeout -k 10 600 python3 bench.py --full --steps 3 --warmup 1 > $OUT/bench_T1.log 2>&1 \
+ && timeout -k 10 600 python3 bench.py --full --workload map --steps 5 --warmup 1 > $OUT/bench_M2.log 2>&1 \
  && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_T1 -o run -- $B --steps 2 --warmup 1 > $OUT/trace_T1.log 2>&1 \
  && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_M2 -o run -- $B --workload map --steps 2 --warmup 1 > $OUT/trace_M2.log 2>&1 \
  && timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_T1 -o run -- $B --steps 1 --warmup 0 > $OUT/pmc_fetch_T1.log 2>&1 \

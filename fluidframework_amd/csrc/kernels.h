@@ -62,7 +62,7 @@ struct MtDeviceOut {
   fmt_mt_propset* props;       // nDocs * capProps
   fmt_mt_catchup_range* catchup;  // slabs at catchupOffsets, or nullptr
   fmt_mt_remove_order* rmOrder;   // slabs at rmOrderOffsets, or nullptr
-  uint32_t* ckpt;                 // plain batches: per-document compact → small tier checkpoints, or nullptr
+  uint32_t* ckpt;                 // plain batches: per-document register-tier checkpoints (one slot each), or nullptr
   // large tier over a plain batch: the small tier's result slabs, where it left its checkpoints
   const fmt_mt_leaf* smallLeaves;
   const uint16_t* smallChars;
@@ -116,15 +116,18 @@ struct MtCaps {
 };
 MtCaps mergeTreeCaps(bool large);
 
-// Compact + small tiers: replays documents docList[0..count) (or all docs when docList == nullptr);
-// documents that overflow the small tier are listed in esc (esc[0] = count, then ids) when esc !=
-// nullptr. A plain batch (no obliterates, no remove order) with esc2 != nullptr starts in the compact
-// tier and lists its overflow in esc2 (count + 1 entries) for the small tier. esc[0] and esc2[0] must
-// be zero before the call. sched: 3 zeroed device counters (compact, small, large) from which the
-// tiers deal documents to waves dynamically (nullptr: static grid-stride shares). adjust: the batch
-// holds annotate-adjust entries (the Adj engine variants, small tier first, no checkpoints).
+// Micro + compact + small tiers: replays documents docList[0..count) (or all docs when docList ==
+// nullptr); documents that overflow the small tier are listed in esc (esc[0] = count, then ids) when
+// esc != nullptr. A batch without remove order with esc2 != nullptr starts in the compact tier and
+// lists its overflow in esc2 (count + 1 entries) for the small tier; without obliterates either and
+// with esc4 != nullptr it starts in the micro tier (mergetree_micro.hip), whose overflow list the
+// compact tier replays, listing its own in esc4 (count + 1 entries). esc3 (count + 1 entries): where a
+// list is reordered by remaining ops. esc[0], esc2[0] and esc4[0] must be zero before the call. sched:
+// 4 zeroed device counters (compact, small, large, micro) from which the tiers deal documents to waves
+// dynamically (nullptr: static grid-stride shares). adjust: the batch holds annotate-adjust entries
+// (the Adj engine variants, small tier first, no checkpoints).
 hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, int numCUs,
+                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
                            hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust);
 
 // Large tier over docList[0..count): out.leaves/chars/props are slabs indexed by list position.

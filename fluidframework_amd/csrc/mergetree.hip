@@ -1,10 +1,11 @@
 // mergetree.hip — merge-tree replay, small tier (8 register rows: 512 leaves, 2 waves/SIMD), the
 // overflow-list kernel and the tier cascade (kernel template: mergetree_kernel.h).
 //
-// A plain batch replays every document in the compact tier first (mergetree_compact.hip: 4 rows,
-// 3 waves/SIMD); the documents it overflows replay in this tier from a device-side list; those this
-// tier overflows go to the large tier (mergetree_large.hip) after the host reads the list length.
-// Batches holding obliterates or remove-order recording start in this tier.
+// A plain batch replays every document in the micro tier first (mergetree_micro.hip: 2 rows); the
+// documents it overflows go on in the compact tier (mergetree_compact.hip: 4 rows) from a device-side
+// list, and those that one overflows in this tier from a second list; those this tier overflows go to
+// the large tier (mergetree_large.hip) after the host reads the list length. Batches with obliterates
+// start in the compact tier; batches with remove-order recording or adjusts start in this tier.
 #define FMT_MT_COLLECT_DEFINE 1
 #include "mergetree_kernel.h"
 
@@ -13,12 +14,13 @@ namespace fmt_kernels {
 constexpr int kMtWaves = 4;  // small tier: 4 documents per workgroup, 2 waves/SIMD
 
 int mergeTreeProfileCompact(uint64_t* out, int n, bool reset);
+int mergeTreeProfileMicro(uint64_t* out, int n, bool reset);
 int mergeTreeProfileLarge(uint64_t* out, int n, bool reset);
 
 int mergeTreeProfile(uint64_t* out, int n, bool reset) {
   for (int c = 0; c < n; c++) out[c] = 0;
   if (addTuProfile(out, n, reset) < 0 || mergeTreeProfileCompact(out, n, reset) < 0 ||
-      mergeTreeProfileLarge(out, n, reset) < 0)
+      mergeTreeProfileMicro(out, n, reset) < 0 || mergeTreeProfileLarge(out, n, reset) < 0)
     return -1;
   return fmt_mt::kPfCount;
 }
@@ -35,11 +37,13 @@ size_t mergeTreeCheckpointBytes() { return sizeof(uint32_t) * fmt_mt::Doc<false,
 
 hipError_t launchMergeTreeCompact(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
                                   uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next,
-                                  bool obliterate);
+                                  bool obliterate, const uint32_t* countDev);
+hipError_t launchMergeTreeMicro(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
+                                uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next);
 
-// The compact tier's overflow list in[0] = n, in[1..n] reordered into out by remaining ops,
+// A tier's overflow list in[0] = n, in[1..n] reordered into out by remaining ops,
 // longest first (64 buckets between 0 and the largest remainder): with documents dealt to waves
-// in list order, the small-tier pass then ends on short documents (longest-processing-time first).
+// in list order, the next tier's pass then ends on short documents (longest-processing-time first).
 // A checkpointed document has ops [ckpt next, end) left, any other one its whole stream.
 constexpr int kOrderBuckets = 64;
 __global__ __launch_bounds__(1024) void orderByRemainingKernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(1024) void orderByRemainingKernel(const uint32_t* _
 
 // Variants: obliterates (Ob) and/or the remove-order recording of SnapshotV1 batches (Rm).
 hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, int numCUs,
+                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
                            hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust) {
   using S = fmt_mt::SmallTier;
   uint32_t* n1 = sched ? sched + 1 : nullptr;
@@ -104,13 +108,39 @@ hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, c
     return launchTier<false, S, true, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
   if (esc == nullptr || esc2 == nullptr)
     return launchTier<false, S, false, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  // compact tier over everything → overflow list esc2 → this tier over that list → overflow list esc
-  hipError_t e = launchMergeTreeCompact(batch, out, docList, count, esc2, numCUs, stream, sched, obliterate);
+  constexpr uint32_t kCkptWords = static_cast<uint32_t>(fmt_mt::Doc<false, fmt_mt::CompactTier>::kCkptWords);
+  const bool order = esc3 != nullptr && out.ckpt != nullptr;  // longest remaining streams first
+  hipError_t e;
+  if (!obliterate && esc4 != nullptr) {
+    // micro tier over everything → overflow list esc2 (ordered: esc3) → compact tier over that list →
+    // overflow list esc4 (ordered: esc2 again, free by then) → this tier over that list → overflow list
+    // esc. Without checkpoints (out.ckpt == nullptr) each tier restarts its documents from their first op.
+    e = launchMergeTreeMicro(batch, out, docList, count, esc2, numCUs, stream, sched ? sched + 3 : nullptr);
+    if (e != hipSuccess) return e;
+    uint32_t* list = esc2;
+    if (order) {
+      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc2, esc3, out.headers,
+                         batch.docOpOffsets, out.ckpt, kCkptWords);
+      list = esc3;
+    }
+    e = launchMergeTreeCompact(batch, out, list + 1, count, esc4, numCUs, stream, sched, false, list);
+    if (e != hipSuccess) return e;
+    if (order) {
+      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc4, esc2, out.headers,
+                         batch.docOpOffsets, out.ckpt, kCkptWords);
+      list = esc2;
+    } else {
+      list = esc4;
+    }
+    return launchTier<false, S, false, kMtWaves, 2>(batch, out, list + 1, count, esc, numCUs, stream, list, n1);
+  }
+  // obliterate batches: compact tier over everything → overflow list esc2 → this tier over that list →
+  // overflow list esc
+  e = launchMergeTreeCompact(batch, out, docList, count, esc2, numCUs, stream, sched, obliterate, nullptr);
   if (e != hipSuccess) return e;
-  if (esc3 != nullptr && out.ckpt != nullptr) {  // longest remaining streams first
+  if (order) {
     hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc2, esc3, out.headers,
-                       batch.docOpOffsets, out.ckpt,
-                       static_cast<uint32_t>(fmt_mt::Doc<false, fmt_mt::CompactTier>::kCkptWords));
+                       batch.docOpOffsets, out.ckpt, kCkptWords);
     esc2 = esc3;
   }
   if (obliterate)

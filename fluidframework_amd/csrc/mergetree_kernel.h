@@ -1,6 +1,6 @@
 // mergetree_kernel.h — the merge-tree replay kernel template (mt_engine.h) and its launcher, shared
 // by the per-tier translation units (mergetree.hip: small tier; mergetree_compact.hip: compact tier;
-// mergetree_large.hip: large tier), which compile in parallel.
+// mergetree_micro.hip: micro tier; mergetree_large.hip: large tier), which compile in parallel.
 //
 // One wavefront replays one document end to end; several documents share a workgroup, each with its
 // own LDS state (fmt_mt::Scratch). Documents are independent, so the grid simply strides over them;
@@ -133,7 +133,9 @@ __global__ __launch_bounds__(64 * Waves, WavesPerEU) void mergeTreeKernel(MtDevi
     }
     if (Doc::kSavesCkpt || Doc::kResumesCkpt || (Ob && Doc::kResumesBig)) {  // (large tier: live obliterates)
       o.ckpt = out.ckpt ? out.ckpt + static_cast<size_t>(d) * Doc::kCkptWords : nullptr;
-      o.ckptResume = Doc::kResumesCkpt && o.ckpt != nullptr &&
+      // (a tier that also saves — the compact one — resumes only over an overflow list: over every
+      // document it is the first tier, and the headers hold whatever an earlier run left)
+      o.ckptResume = Doc::kResumesCkpt && (!Doc::kSavesCkpt || countDev != nullptr) && o.ckpt != nullptr &&
                      __builtin_amdgcn_readfirstlane(out.headers[d].status) == fmt_mt::kCkptEscalate;
     } else {
       o.ckpt = nullptr;

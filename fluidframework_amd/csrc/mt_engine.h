@@ -53,7 +53,7 @@ constexpr int kKeyChunks = kKeysMax / 64;        // slot k = chunk k / 64, lane 
 static_assert(kKeysMax % 64 == 0, "prop-set slots come in whole waves");
 constexpr int32_t kNotRemoved = 0x7fffffff;
 constexpr int kCapacityFinal = -33;  // internal status (small tier only), never leaves the runtime
-constexpr int kCkptEscalate = -34;   // internal status: the compact tier stopped at a checkpoint (Doc::saveCkpt)
+constexpr int kCkptEscalate = -34;   // internal status: a tier stopped the document at a checkpoint (Doc::saveCkpt / saveBig)
 
 // Capacity tiers. Every document first replays in the small tier (leaves in 40 VGPRs, text in
 // LDS, 2 waves/SIMD). A document that overflows it (FMT_E_CAPACITY) is replayed again from its
@@ -87,6 +87,16 @@ struct CompactTier : SmallTier {
   static constexpr int kRows = 4;
   static constexpr int kCapChars = 2048;  // 12 waves/CU × 11232 B of Scratch
   using VR = V4;
+};
+
+// The micro tier: 2 register rows (128 leaves) and half the compact tier's text. Every row loop is
+// unrolled over kRows, so a document pays for each row of its tier on every op whether it has leaves
+// there or not; half of the T1 ops run on documents that fit two rows. Plain batches
+// only (mergetree_micro.hip); a document that outgrows it goes on in the compact tier from a checkpoint.
+struct MicroTier : SmallTier {
+  static constexpr int kRows = 2;
+  static constexpr int kCapChars = 1024;  // Scratch without the obliterate table: 7264 B per wave
+  using VR = V2;
 };
 
 struct LargeTier {
@@ -352,14 +362,17 @@ class Doc {
   Lane<uint32_t> rmHits;  // leaves a flagged REMOVE found already removed (row bitmask per lane)
 
   // ------------------------------------------------------------------ tier checkpoint
-  // A document without remove-order recording in the compact tier that is about to outgrow its 4
-  // register rows stops before the op (one op adds at most two leaves: an insert's split plus the
-  // new leaf, or a range op's — obliterate's too — two boundary splits) and leaves its whole state
-  // in its HBM checkpoint: the scalars, the leaf words of the compact rows and the LDS scratch (same
-  // layout in both tiers). The small tier resumes it from that op instead of replaying it from its
-  // first op.
-  static constexpr bool kSavesCkpt = !C::kHbmChars && C::kRows < SmallTier::kRows && !Rm && !Loc;
-  static constexpr bool kResumesCkpt = !C::kHbmChars && C::kRows == SmallTier::kRows && !Rm && !Loc;
+  // A document without remove-order recording in a register tier below the small one (micro: 2
+  // rows, compact: 4) that is about to outgrow its rows stops before the op (one op adds at most two
+  // leaves: an insert's split plus the new leaf, or a range op's — obliterate's too — two boundary
+  // splits) and leaves its state in its HBM checkpoint: the scalars, the leaf words of its live rows,
+  // its text and the LDS scratch (same layout in every register tier). The next tier up (compact
+  // after micro, small after compact) resumes it from that op instead of replaying it from its first
+  // op; the compact tier may save again into the slot it resumed from.
+  static constexpr bool kRegTier = !C::kHbmChars && !Rm && !Loc;
+  static constexpr bool kSavesCkpt = kRegTier && C::kRows < SmallTier::kRows;
+  // (the micro tier takes no obliterate batches, so the compact tier's Ob variant has nothing to resume)
+  static constexpr bool kResumesCkpt = kRegTier && (C::kRows == SmallTier::kRows || (C::kRows > MicroTier::kRows && !Ob));
   // layout: 16 head words | leaf words of the compact rows | the compact tier's chars | the rest of
   // the scratch (blk .. tmp: the same fields in both tiers; only the chars array differs in size) |
   // the live obliterates (ob .. obStart; Ob only, head words 13..15 hold their counts and bitmap)
@@ -623,11 +636,15 @@ class Doc {
         }
       }
     }
+    // only the live part: rows below rows() (head word 2 = n gives their count) and, below, the first
+    // nChars text units (head word 3); restoreCkpt zero-fills the other rows itself
+    const int nr = rows();
     FOR_LANES(l) {
 #pragma unroll
       for (int f = 0; f < 5; f++) {
 #pragma unroll
-        for (int r = 0; r < kCkptRows && r < kRows; r++) ck[kCkptHead + (f * kCkptRows + r) * 64 + l] = LANE(W[f])[r];
+        for (int r = 0; r < kCkptRows && r < kRows; r++)
+          if (r < nr) ck[kCkptHead + (f * kCkptRows + r) * 64 + l] = LANE(W[f])[r];
       }
     }
     waveSync();  // every LDS write of the op stream has landed
@@ -669,12 +686,13 @@ class Doc {
       obUsed = uni(ck[14]) | (static_cast<uint64_t>(uni(ck[15])) << 32);
     }
     status = FMT_OK;
+    const int nr = rows();  // the rows the saver wrote (it had at most kCkptRows); the others are empty
     FOR_LANES(l) {
 #pragma unroll
       for (int f = 0; f < 5; f++) {
         VR z;
 #pragma unroll
-        for (int r = 0; r < kRows; r++) z[r] = r < kCkptRows ? ck[kCkptHead + (f * kCkptRows + r) * 64 + l] : 0u;
+        for (int r = 0; r < kRows; r++) z[r] = r < kCkptRows && r < nr ? ck[kCkptHead + (f * kCkptRows + r) * 64 + l] : 0u;
         LANE(W[f]) = z;
       }
     }

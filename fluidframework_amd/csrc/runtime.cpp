@@ -149,6 +149,7 @@ struct fmt_ctx {
   DevBuf<uint32_t> mtEsc;                    // small-tier overflow list: [0] = count, then doc ids
   DevBuf<uint32_t> mtEsc2;                   // compact-tier overflow list (no remove order), same layout
   DevBuf<uint32_t> mtEsc3;                   // the same list, longest remaining streams first
+  DevBuf<uint32_t> mtEsc4;                   // plain batches: the compact tier's list when the micro tier's is in mtEsc2
   DevBuf<uint32_t> mtCkpt;                   // per-document compact → small tier checkpoints
   DevBuf<uint32_t> mtHugeCk;                 // per large-tier slot: its large → huge checkpoint record (huge_ckpt.h)
   bool mtCkptOk = false;                     // allocated for this batch (else tiers replay overflow from op 0)
@@ -440,6 +441,7 @@ void fmt_close(fmt_ctx* c) {
   c->mtEsc.release();
   c->mtEsc2.release();
   c->mtEsc3.release();
+  c->mtEsc4.release();
   c->mtSched.release();
   c->mtCkpt.release();
   c->mtHugeCk.release();
@@ -1119,6 +1121,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   FMT_HIP(c, c->mtEsc.reserve(n + 1ull));
   FMT_HIP(c, c->mtEsc2.reserve(n + 1ull));
   FMT_HIP(c, c->mtEsc3.reserve(n + 1ull));
+  FMT_HIP(c, c->mtEsc4.reserve(n + 1ull));
   FMT_HIP(c, c->mtSched.reserve(4));
   c->mtBigSlot.assign(n, -1);
   // Catch-up slabs: kCatchupPerOp ranges per flagged op plus kCatchupPerDoc per document that has
@@ -1342,8 +1345,9 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   c->mtNProps = b->n_props_ops;
   c->mtHasInit = b->doc_init != nullptr;
   c->mtObliterate = obliterates;
-  // A batch without remove-order recording starts in the compact tier; a document about to outgrow
-  // it stops at a checkpoint (≈17 KiB per document) that the small tier resumes from.
+  // A batch without remove-order recording starts in the micro tier (with obliterates: the compact
+  // tier); a document about to outgrow a tier stops at a checkpoint (one slot of ≈17 KiB per document)
+  // that the next tier resumes from.
   c->mtCkptOk = false;
   if (!c->mtHasRmOrder) {
     // (a batch too large for the checkpoints still replays: overflowing documents then restart in
@@ -1497,6 +1501,7 @@ int fmt_mt_run(fmt_ctx* c) {
                                 c->mtHasAdjust ? c->mtLegacy.p : nullptr};
   FMT_HIP(c, hipMemsetAsync(c->mtEsc.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtEsc2.p, 0, sizeof(uint32_t), c->stream));
+  FMT_HIP(c, hipMemsetAsync(c->mtEsc4.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtSched.p, 0, 4 * sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
   const bool hasHuge = c->mtHugeLoaded > 0, list = c->mtUseList;
@@ -1510,7 +1515,7 @@ int fmt_mt_run(fmt_ctx* c) {
                                                    c->mtHasAdjust));
   } else if (!list || c->mtNSmall > 0)
     FMT_HIP(c, fmt_kernels::launchMergeTree(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
-                                            c->mtEsc.p, c->mtEsc2.p, c->mtEsc3.p, c->numCUs, c->stream,
+                                            c->mtEsc.p, c->mtEsc2.p, c->mtEsc3.p, c->mtEsc4.p, c->numCUs, c->stream,
                                             c->mtObliterate,
                                             c->mtHasRmOrder, c->mtSched.p, c->mtHasAdjust));
   if (hasHuge)

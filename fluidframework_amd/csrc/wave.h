@@ -28,6 +28,7 @@ struct Lane {
 // register-relative moves (M0 / set_gpr_idx), never to scratch memory.
 typedef uint32_t V8 __attribute__((ext_vector_type(8)));
 typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+typedef uint32_t V2 __attribute__((ext_vector_type(2)));
 typedef uint32_t VKV __attribute__((ext_vector_type(FMT_MT_PROPS_MAX)));  // one prop set's (key, value) words
 #define LANE(x) ((x).v)
 #define FOR_LANES(l) for ([[maybe_unused]] int l = static_cast<int>(__lane_id()), l##_once = 1; l##_once; l##_once = 0)
@@ -38,6 +39,7 @@ FMT_DEV int waveLane() { return static_cast<int>(__lane_id()); }
 // variable-index load from the enclosing object's stack slot (which would put it in scratch).
 FMT_DEV void launder(V8& v) { asm volatile("" : "+v"(v)); }
 FMT_DEV void launder(V4& v) { asm volatile("" : "+v"(v)); }
+FMT_DEV void launder(V2& v) { asm volatile("" : "+v"(v)); }
 
 // Large-tier rows: a plain per-lane array indexed at run time (private memory), so the row loops
 // stay rolled and the 32-row engine compiles in seconds.
@@ -224,6 +226,11 @@ using V8 = VecN<8>;
 using V32 = VecN<32>;
 struct V4 {
   uint32_t x[4];
+  uint32_t& operator[](int i) { return x[i]; }
+  const uint32_t& operator[](int i) const { return x[i]; }
+};
+struct V2 {
+  uint32_t x[2];
   uint32_t& operator[](int i) { return x[i]; }
   const uint32_t& operator[](int i) const { return x[i]; }
 };

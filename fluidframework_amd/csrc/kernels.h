@@ -72,6 +72,8 @@ struct MtDeviceOut {
   // large tier over a plain batch: per large-tier slot, its large → huge checkpoint record
   // (huge_ckpt.h, fmt_ckpt::kWords words), or nullptr
   uint32_t* hugeCkpt = nullptr;
+  // set by launchMergeTree for the rounds of a plain batch in which documents may step down a tier
+  bool descend = false;
 };
 // Bytes of one document's tier checkpoint (mt_engine.h Doc::kCkptWords).
 size_t mergeTreeCheckpointBytes();
@@ -125,10 +127,14 @@ MtCaps mergeTreeCaps(bool large);
 // list is reordered by remaining ops. esc[0], esc2[0] and esc4[0] must be zero before the call. sched:
 // 4 zeroed device counters (compact, small, large, micro) from which the tiers deal documents to waves
 // dynamically (nullptr: static grid-stride shares). adjust: the batch holds annotate-adjust entries
-// (the Adj engine variants, small tier first, no checkpoints).
+// (the Adj engine variants, small tier first, no checkpoints). desc: mergeTreeDescendWords(count) zeroed
+// words (the lists and dealing counters of the rounds in which documents that shrank step down a tier:
+// plain batches with checkpoints and esc3), or nullptr: one round, a document only ever moves up.
 hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
                            uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
-                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust);
+                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust,
+                           uint32_t* desc = nullptr);
+size_t mergeTreeDescendWords(uint32_t count);
 
 // Large tier over docList[0..count): out.leaves/chars/props are slabs indexed by list position.
 hipError_t launchMergeTreeLarge(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,

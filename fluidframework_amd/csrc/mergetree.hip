@@ -4,8 +4,13 @@
 // A plain batch replays every document in the micro tier first (mergetree_micro.hip: 2 rows); the
 // documents it overflows go on in the compact tier (mergetree_compact.hip: 4 rows) from a device-side
 // list, and those that one overflows in this tier from a second list; those this tier overflows go to
-// the large tier (mergetree_large.hip) after the host reads the list length. Batches with obliterates
-// start in the compact tier; batches with remove-order recording or adjusts start in this tier.
+// the large tier (mergetree_large.hip) after the host reads the list length. With checkpoints the
+// compact and small tiers run kDescendRounds times: in every round but the last a small-tier document
+// that shrank to half of the compact tier stops (fmt_mt::kCkptDescend) and goes on a "down" list, which
+// the compact tier replays in the next round, so it pays for the rows it has, not for the rows it once
+// had. Every list length stays on the device; a round whose lists are empty costs launches that exit
+// at once. Batches with obliterates start in the compact tier; batches with remove-order recording or
+// adjusts start in this tier; neither steps down.
 #define FMT_MT_COLLECT_DEFINE 1
 #include "mergetree_kernel.h"
 
@@ -41,6 +46,17 @@ hipError_t launchMergeTreeCompact(const MtDeviceBatch& batch, const MtDeviceOut&
 hipError_t launchMergeTreeMicro(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
                                 uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next);
 
+// Rounds of the plain cascade (see the header comment). DESIGN.md §4.1 has the hop counts behind it.
+#ifndef FMT_DESCEND_ROUNDS
+#define FMT_DESCEND_ROUNDS 2
+#endif
+constexpr int kDescendRounds = FMT_DESCEND_ROUNDS;  // (1: a document only ever moves up)
+constexpr size_t kDescendHead = 64;  // dealing counters of the rounds after the first, 2 a round
+
+size_t mergeTreeDescendWords(uint32_t count) {
+  return kDescendHead + static_cast<size_t>(2 * (kDescendRounds - 1)) * (static_cast<size_t>(count) + 1);
+}
+
 // A tier's overflow list in[0] = n, in[1..n] reordered into out by remaining ops,
 // longest first (64 buckets between 0 and the largest remainder): with documents dealt to waves
 // in list order, the next tier's pass then ends on short documents (longest-processing-time first).
@@ -57,7 +73,7 @@ __global__ __launch_bounds__(1024) void orderByRemainingKernel(const uint32_t* _
   __syncthreads();
   auto remaining = [&](uint32_t d) -> uint32_t {
     uint64_t first = offs[d];
-    if (headers[d].status == fmt_mt::kCkptEscalate) {
+    if (headers[d].status == fmt_mt::kCkptEscalate || headers[d].status == fmt_mt::kCkptDescend) {
       const uint32_t* h = ckpt + static_cast<size_t>(d) * ckptWords;
       first = h[0] | (static_cast<uint64_t>(h[1]) << 32);
     }
@@ -90,7 +106,8 @@ __global__ __launch_bounds__(1024) void orderByRemainingKernel(const uint32_t* _
 // Variants: obliterates (Ob) and/or the remove-order recording of SnapshotV1 batches (Rm).
 hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
                            uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
-                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust) {
+                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust,
+                           uint32_t* desc) {
   using S = fmt_mt::SmallTier;
   uint32_t* n1 = sched ? sched + 1 : nullptr;
   if (adjust) {  // annotate-adjust batches: the Adj variants, small tier over every document (no checkpoints)
@@ -112,27 +129,40 @@ hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, c
   const bool order = esc3 != nullptr && out.ckpt != nullptr;  // longest remaining streams first
   hipError_t e;
   if (!obliterate && esc4 != nullptr) {
-    // micro tier over everything → overflow list esc2 (ordered: esc3) → compact tier over that list →
-    // overflow list esc4 (ordered: esc2 again, free by then) → this tier over that list → overflow list
-    // esc. Without checkpoints (out.ckpt == nullptr) each tier restarts its documents from their first op.
+    // Round 0: micro tier over everything → overflow list esc2 → compact tier over that list → overflow
+    // list esc4 → this tier over that list → overflow list esc. Every list is reordered into esc3 first
+    // (order). Without checkpoints (out.ckpt == nullptr) each tier restarts its documents from their
+    // first op, and nothing steps down.
+    // Round r > 0 (desc: two lists a round): compact tier over this tier's down list of round r - 1 →
+    // this tier over the compact tier's overflow → esc, appended. The last round lets nothing step
+    // down, so every document finishes (or is in esc).
+    const int rounds = order && desc != nullptr ? kDescendRounds : 1;
+    const size_t stride = static_cast<size_t>(count) + 1;
+    const auto roundList = [&](int r, int k) { return desc + kDescendHead + (static_cast<size_t>(2 * (r - 1) + k)) * stride; };
+    const auto ordered = [&](uint32_t* list) {
+      if (!order) return list;
+      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, list, esc3, out.headers,
+                         batch.docOpOffsets, out.ckpt, kCkptWords);
+      return esc3;
+    };
     e = launchMergeTreeMicro(batch, out, docList, count, esc2, numCUs, stream, sched ? sched + 3 : nullptr);
     if (e != hipSuccess) return e;
-    uint32_t* list = esc2;
-    if (order) {
-      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc2, esc3, out.headers,
-                         batch.docOpOffsets, out.ckpt, kCkptWords);
-      list = esc3;
+    for (int r = 0; r < rounds; r++) {
+      MtDeviceOut o = out;
+      o.descend = r + 1 < rounds;
+      uint32_t* toCompact = r == 0 ? esc2 : roundList(r, 0);
+      uint32_t* toSmall = r == 0 ? esc4 : roundList(r, 1);
+      uint32_t* down = o.descend ? roundList(r + 1, 0) : nullptr;  // → the next round's compact tier
+      uint32_t* deal = sched && r > 0 ? desc + 2 * (r - 1) : nullptr;
+      const uint32_t* list = ordered(toCompact);
+      e = launchMergeTreeCompact(batch, o, list + 1, count, toSmall, numCUs, stream, r == 0 ? sched : deal, false, list);
+      if (e != hipSuccess) return e;
+      list = ordered(toSmall);
+      e = launchTier<false, S, false, kMtWaves, 2>(batch, o, list + 1, count, esc, numCUs, stream, list,
+                                                   r == 0 ? n1 : (deal ? deal + 1 : nullptr), down);
+      if (e != hipSuccess) return e;
     }
-    e = launchMergeTreeCompact(batch, out, list + 1, count, esc4, numCUs, stream, sched, false, list);
-    if (e != hipSuccess) return e;
-    if (order) {
-      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc4, esc2, out.headers,
-                         batch.docOpOffsets, out.ckpt, kCkptWords);
-      list = esc2;
-    } else {
-      list = esc4;
-    }
-    return launchTier<false, S, false, kMtWaves, 2>(batch, out, list + 1, count, esc, numCUs, stream, list, n1);
+    return hipSuccess;
   }
   // obliterate batches: compact tier over everything → overflow list esc2 → this tier over that list →
   // overflow list esc

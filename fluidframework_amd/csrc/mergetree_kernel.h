@@ -135,8 +135,11 @@ __global__ __launch_bounds__(64 * Waves, WavesPerEU) void mergeTreeKernel(MtDevi
       o.ckpt = out.ckpt ? out.ckpt + static_cast<size_t>(d) * Doc::kCkptWords : nullptr;
       // (a tier that also saves — the compact one — resumes only over an overflow list: over every
       // document it is the first tier, and the headers hold whatever an earlier run left)
+      // (kCkptDescend: the tier above left it, see launchMergeTree's rounds)
+      const int st = __builtin_amdgcn_readfirstlane(out.headers[d].status);
       o.ckptResume = Doc::kResumesCkpt && (!Doc::kSavesCkpt || countDev != nullptr) && o.ckpt != nullptr &&
-                     __builtin_amdgcn_readfirstlane(out.headers[d].status) == fmt_mt::kCkptEscalate;
+                     (st == fmt_mt::kCkptEscalate || (!Ob && st == fmt_mt::kCkptDescend));
+      if constexpr (Doc::kDescends) o.descend = out.descend;
     } else {
       o.ckpt = nullptr;
       o.ckptResume = false;
@@ -170,15 +173,17 @@ __global__ __launch_bounds__(64 * Waves, WavesPerEU) void mergeTreeKernel(MtDevi
 
 // The documents a tier could not hold (FMT_E_CAPACITY) among docList[0..nDocs) (nDocs = countDev[0]
 // when set): esc[0] = count, esc[1..] = ids. A limit the large tier shares (fmt_mt::kCapacityFinal)
-// is reported as FMT_E_CAPACITY without escalation. Defined in mergetree.hip.
+// is reported as FMT_E_CAPACITY without escalation. down (or nullptr: the launch let none step down):
+// the same for the documents that stopped for the tier below (fmt_mt::kCkptDescend). Both lists are
+// appended to, so two launches can fill one. Defined in mergetree.hip.
 __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* __restrict__ headers,
                                                              const uint32_t* __restrict__ docList, uint32_t nDocs,
-                                                             const uint32_t* countDev, uint32_t* esc);
+                                                             const uint32_t* countDev, uint32_t* esc, uint32_t* down);
 
 #ifdef FMT_MT_COLLECT_DEFINE
 __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* __restrict__ headers,
                                                              const uint32_t* __restrict__ docList, uint32_t nDocs,
-                                                             const uint32_t* countDev, uint32_t* esc) {
+                                                             const uint32_t* countDev, uint32_t* esc, uint32_t* down) {
   if (countDev != nullptr) nDocs = *countDev;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nDocs; i += gridDim.x * blockDim.x) {
     const uint32_t d = docList ? docList[i] : i;
@@ -187,6 +192,9 @@ __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* 
     if (st == FMT_E_CAPACITY || st == fmt_mt::kCkptEscalate) {
       const uint32_t k = atomicAdd(esc, 1u);
       esc[1 + k] = d;
+    } else if (down != nullptr && st == fmt_mt::kCkptDescend) {
+      const uint32_t k = atomicAdd(down, 1u);
+      down[1 + k] = d;
     }
   }
 }
@@ -196,7 +204,7 @@ __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* 
 template <bool Ob, class C, bool Rm, int Waves, int WavesPerEU, bool Adj = false, bool Loc = false>
 static hipError_t launchTier(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
                              uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream,
-                             const uint32_t* countDev = nullptr, uint32_t* next = nullptr) {
+                             const uint32_t* countDev = nullptr, uint32_t* next = nullptr, uint32_t* down = nullptr) {
   const size_t lds = scratchBytes<C, Ob>() * Waves;
   // One resident wave of workgroups: every workgroup strides over the same number of documents,
   // so none waits behind the residency limit (VGPRs cap the small tier at 2 waves/SIMD).
@@ -212,7 +220,7 @@ static hipError_t launchTier(const MtDeviceBatch& batch, const MtDeviceOut& out,
   if (esc != nullptr) {  // over the documents this launch replayed
     const uint32_t g = (count + 255) / 256;
     hipLaunchKernelGGL(collectOverflowKernel, dim3(g < 1024 ? (g > 0 ? g : 1) : 1024), dim3(256), 0, stream, out.headers,
-                       docList, count, countDev, esc);
+                       docList, count, countDev, esc, down);
   }
   return hipGetLastError();
 }

@@ -54,6 +54,16 @@ static_assert(kKeysMax % 64 == 0, "prop-set slots come in whole waves");
 constexpr int32_t kNotRemoved = 0x7fffffff;
 constexpr int kCapacityFinal = -33;  // internal status (small tier only), never leaves the runtime
 constexpr int kCkptEscalate = -34;   // internal status: a tier stopped the document at a checkpoint (Doc::saveCkpt / saveBig)
+// internal status: a plain document shrank enough for the tier below and stopped at a checkpoint
+// (Doc::saveCkpt) that the tier below resumes (-35 is fmt_ckpt::kStatusHuge)
+constexpr int kCkptDescend = -36;
+// Stepping down (plain batches, launches with DocOutputs::descend set): after a message's last member a
+// small-tier document with at most kDescendLeaves4 leaves and kDescendChars4 text units stops for the
+// compact tier, unless fewer than kDescendMinOps ops are left. Half the compact tier's rows and text:
+// the document must double before the compact tier's upward check (n + 2 > 256) sends it up again.
+// (compact → micro was built and measured too and is not kept: DESIGN.md §4.1)
+constexpr int kDescendLeaves4 = 128, kDescendChars4 = 1024;
+constexpr int kDescendMinOps = 128;
 
 // Capacity tiers. Every document first replays in the small tier (leaves in 40 VGPRs, text in
 // LDS, 2 waves/SIMD). A document that overflows it (FMT_E_CAPACITY) is replayed again from its
@@ -259,6 +269,8 @@ struct DocOutputs {
   uint16_t* legacyProps;
   // large tier, plain batches: the document's large → huge checkpoint record (huge_ckpt.h), or nullptr
   uint32_t* hugeCkpt = nullptr;
+  // plain batches, small tier: stop a document that fits half of the compact tier (kCkptDescend)
+  bool descend = false;
 };
 
 // Diagnostic build only (FMT_PROFILE=1): per-phase shader-clock totals, see stamp().
@@ -373,6 +385,17 @@ class Doc {
   static constexpr bool kSavesCkpt = kRegTier && C::kRows < SmallTier::kRows;
   // (the micro tier takes no obliterate batches, so the compact tier's Ob variant has nothing to resume)
   static constexpr bool kResumesCkpt = kRegTier && (C::kRows == SmallTier::kRows || (C::kRows > MicroTier::kRows && !Ob));
+  // Stepping down (kCkptDescend): plain batches only, from the small tier to the compact tier. The
+  // register tiers share blocks, heap, prop sets and writers; rows and text are what the compact tier
+  // has less of.
+  static constexpr bool kDescends = kRegTier && !Ob && !Adj && C::kRows == SmallTier::kRows;
+  static constexpr int kDescendLeaves = kDescendLeaves4;
+  static constexpr int kDescendChars = kDescendChars4;
+  static_assert(SmallTier::kMaxBlocks == CompactTier::kMaxBlocks && SmallTier::kPropCap == CompactTier::kPropCap &&
+                    SmallTier::kMaxClient == CompactTier::kMaxClient && SmallTier::kHeapCap == CompactTier::kHeapCap &&
+                    2 * kDescendLeaves4 <= 64 * CompactTier::kRows && 2 * kDescendChars4 <= CompactTier::kCapChars,
+                "a document that steps down fits the compact tier with half of it to spare");
+  bool descend = false;
   // layout: 16 head words | leaf words of the compact rows | the compact tier's chars | the rest of
   // the scratch (blk .. tmp: the same fields in both tiers; only the chars array differs in size) |
   // the live obliterates (ob .. obStart; Ob only, head words 13..15 hold their counts and bitmap)
@@ -4085,6 +4108,16 @@ class Doc {
         failSeq = op.seq;
         break;
       }
+      if constexpr (kDescends) {
+        // the document fits the tier below with half of it to spare (and the margins of the upward
+        // check on blocks and prop sets): run() saves it, the tier below resumes at the next op
+        if (descend && lastMember && n <= kDescendLeaves && nChars <= kDescendChars && nFree >= 16 &&
+            nProps <= kPropCap - 4 && i + 1 + kDescendMinOps <= in.end) {
+          ckptNext = i + 1;
+          status = kCkptDescend;
+          return;
+        }
+      }
     }
   }
 
@@ -4249,6 +4282,7 @@ class Doc {
       else loadInitial();
     }
     hugeCkpt = out.hugeCkpt;
+    if constexpr (kDescends) descend = out.descend && ckpt != nullptr;
     if (status == FMT_OK) replay(first);
     if constexpr (kSavesHuge) {
       if (status == kCkptEscalate) {  // the huge tier resumes: the result slabs, then the record
@@ -4258,6 +4292,15 @@ class Doc {
         saveHuge(ckptNext);
         FOR_LANES(l) {
           if (l == 0) out.header->status = fmt_ckpt::kStatusHuge;
+        }
+        return;
+      }
+    }
+    if constexpr (kDescends) {  // small tier: the compact tier's slot layout
+      if (status == kCkptDescend) {
+        saveCkpt(ckptNext);
+        FOR_LANES(l) {
+          if (l == 0) out.header->status = status;
         }
         return;
       }

@@ -151,6 +151,8 @@ struct fmt_ctx {
   DevBuf<uint32_t> mtEsc3;                   // the same list, longest remaining streams first
   DevBuf<uint32_t> mtEsc4;                   // plain batches: the compact tier's list when the micro tier's is in mtEsc2
   DevBuf<uint32_t> mtCkpt;                   // per-document compact → small tier checkpoints
+  DevBuf<uint32_t> mtDesc;                   // plain batches: lists and dealing counters of the step-down rounds
+  size_t mtDescWords = 0;                    // (0: not allocated for this batch, a document only moves up)
   DevBuf<uint32_t> mtHugeCk;                 // per large-tier slot: its large → huge checkpoint record (huge_ckpt.h)
   bool mtCkptOk = false;                     // allocated for this batch (else tiers replay overflow from op 0)
   DevBuf<uint32_t> mtSched;                  // per-tier document counters (dynamic dealing to waves)
@@ -444,6 +446,7 @@ void fmt_close(fmt_ctx* c) {
   c->mtEsc4.release();
   c->mtSched.release();
   c->mtCkpt.release();
+  c->mtDesc.release();
   c->mtHugeCk.release();
   c->mtBigLeaves.release();
   c->mtBigChars.release();
@@ -1356,6 +1359,13 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
                   hipSuccess;
     if (!c->mtCkptOk) (void)hipGetLastError();
   }
+  // plain batches with checkpoints: the lists of the rounds in which documents step down a tier
+  c->mtDescWords = 0;
+  if (c->mtCkptOk && !obliterates && !c->mtHasAdjust && !c->mtLocal) {
+    const size_t words = fmt_kernels::mergeTreeDescendWords(n);
+    if (c->mtDesc.reserve(words) == hipSuccess) c->mtDescWords = words;
+    else (void)hipGetLastError();
+  }
   c->mtInsertChars = insertChars;
   c->mtInitChars = initChars;
   // Huge documents: a summary-loaded document with more segments or text than the large tier holds
@@ -1503,6 +1513,7 @@ int fmt_mt_run(fmt_ctx* c) {
   FMT_HIP(c, hipMemsetAsync(c->mtEsc2.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtEsc4.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtSched.p, 0, 4 * sizeof(uint32_t), c->stream));
+  if (c->mtDescWords > 0) FMT_HIP(c, hipMemsetAsync(c->mtDesc.p, 0, c->mtDescWords * sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
   const bool hasHuge = c->mtHugeLoaded > 0, list = c->mtUseList;
   if (c->mtLocal) {
@@ -1517,7 +1528,8 @@ int fmt_mt_run(fmt_ctx* c) {
     FMT_HIP(c, fmt_kernels::launchMergeTree(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
                                             c->mtEsc.p, c->mtEsc2.p, c->mtEsc3.p, c->mtEsc4.p, c->numCUs, c->stream,
                                             c->mtObliterate,
-                                            c->mtHasRmOrder, c->mtSched.p, c->mtHasAdjust));
+                                            c->mtHasRmOrder, c->mtSched.p, c->mtHasAdjust,
+                                            c->mtDescWords > 0 ? c->mtDesc.p : nullptr));
   if (hasHuge)
     FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates.p, c->hugeInputs.p, c->hugeOuts.p, c->mtHugeLoaded, c->mtHasAdjust, c->mtHasRmOrder, c->stream));
   FMT_HIP(c, hipEventRecord(c->ev1, c->stream));  // device time excludes the host read-back below

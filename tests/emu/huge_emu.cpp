@@ -81,7 +81,7 @@ const fmt_mt_leaf* g_ckLeaves = nullptr;
 const uint16_t* g_ckChars = nullptr;
 const fmt_mt_propset* g_ckProps = nullptr;
 uint64_t g_resumedAt = 0;
-// emu_huge_resume_adj: the large tier's PropertiesManager records and computed numbers of the document
+// emu_huge_resume (annotate-adjust batches): the large tier's PropertiesManager records and computed numbers of the document
 // (in the runtime the huge tier reads the same HBM slabs; the two emulators keep their own)
 const uint32_t* g_seedPm = nullptr;
 uint32_t g_seedPmRecs = 0;
@@ -261,54 +261,23 @@ int emu_huge_replay(const fmt_mt_batch* b, uint32_t d, fmt_mt_doc_result* hdr, f
 }
 
 // Document d resumed in the huge tier from the large tier's checkpoint (emu_mt_replay_large_ckpt: its
-// record ck and its result slabs at large strides, leaves / chars / props of document d). Returns the
-// status; *resumedAt = the op index within the document it resumed at.
+// record ck and its result slabs at large strides, leaves / chars / props of document d), for any flag
+// set the runtime accepts; the variant is the one launchHugeDocs picks (HugeDocT<Adj, Rm>). Returns the
+// status; *resumedAt = the op index within the document it resumed at. Each optional slab is nullptr
+// when the batch does not record that feature:
+//   catchup[capCatchup]  the document's catch-up ranges as the large tier left them (the count is in
+//                        the record); receives the huge tier's after them;
+//   rmOrder[capRm]       its remove-order entries as the large tier left them (leaf ids; the count is
+//                        in the record); receives the final ones;
+//   pm / numsIn          annotate-adjust batches: its PropertiesManager records (pmRecs) and computed
+//                        numbers (nNumsIn) as the large tier left them (emu_mt_adj_slab); legacy / nums /
+//                        *nNums as emu_huge_replay_adj.
 int emu_huge_resume(const fmt_mt_batch* b, uint32_t d, const uint32_t* ck, const fmt_mt_leaf* ckLeaves,
-                    const uint16_t* ckChars, const fmt_mt_propset* ckProps, fmt_mt_doc_result* hdr, fmt_mt_leaf* leaves,
+                    const uint16_t* ckChars, const fmt_mt_propset* ckProps, const uint32_t* pm, uint32_t pmRecs,
+                    const double* numsIn, uint32_t nNumsIn, fmt_mt_doc_result* hdr, fmt_mt_leaf* leaves,
                     uint64_t capLeaves, uint16_t* chars, uint64_t capChars, fmt_mt_propset* props,
-                    fmt_mt_catchup_range* catchup, uint32_t capCatchup, uint64_t* resumedAt) {
-  g_ck = ck;
-  g_ckLeaves = ckLeaves;
-  g_ckChars = ckChars;
-  g_ckProps = ckProps;
-  g_resumedAt = 0;
-  const int st = emu_huge_replay_rec(b, d, hdr, leaves, capLeaves, chars, capChars, props, catchup, capCatchup, nullptr, 0);
-  g_ck = nullptr;
-  g_ckLeaves = nullptr;
-  g_ckChars = nullptr;
-  g_ckProps = nullptr;
-  if (resumedAt) *resumedAt = g_resumedAt;
-  return st;
-}
-
-// emu_huge_resume for a batch with remove-order recording: rmOrder[capRm] holds the document's entries
-// as the large tier left them (leaf ids; the count is in the record) and receives the final ones.
-int emu_huge_resume_rm(const fmt_mt_batch* b, uint32_t d, const uint32_t* ck, const fmt_mt_leaf* ckLeaves,
-                       const uint16_t* ckChars, const fmt_mt_propset* ckProps, fmt_mt_doc_result* hdr, fmt_mt_leaf* leaves,
-                       uint64_t capLeaves, uint16_t* chars, uint64_t capChars, fmt_mt_propset* props,
-                       fmt_mt_remove_order* rmOrder, uint32_t capRm, uint64_t* resumedAt) {
-  g_ck = ck;
-  g_ckLeaves = ckLeaves;
-  g_ckChars = ckChars;
-  g_ckProps = ckProps;
-  g_resumedAt = 0;
-  const int st = emu_huge_replay_rec(b, d, hdr, leaves, capLeaves, chars, capChars, props, nullptr, 0, rmOrder, capRm);
-  g_ck = nullptr;
-  g_ckLeaves = nullptr;
-  g_ckChars = nullptr;
-  g_ckProps = nullptr;
-  if (resumedAt) *resumedAt = g_resumedAt;
-  return st;
-}
-
-// emu_huge_resume for an annotate-adjust batch: pm (pmRecs records) and nums (nNumsIn) are the
-// document's slabs as the large tier left them (emu_mt_adj_slab); legacy / nums / *nNums as
-// emu_huge_replay_adj.
-int emu_huge_resume_adj(const fmt_mt_batch* b, uint32_t d, const uint32_t* ck, const fmt_mt_leaf* ckLeaves,
-                        const uint16_t* ckChars, const fmt_mt_propset* ckProps, const uint32_t* pm, uint32_t pmRecs,
-                        const double* numsIn, uint32_t nNumsIn, fmt_mt_doc_result* hdr, fmt_mt_leaf* leaves,
-                        uint64_t capLeaves, uint16_t* chars, uint64_t capChars, fmt_mt_propset* props, uint16_t* legacy,
-                        double* nums, uint32_t capNums, uint32_t* nNums, uint64_t* resumedAt) {
+                    fmt_mt_catchup_range* catchup, uint32_t capCatchup, fmt_mt_remove_order* rmOrder, uint32_t capRm,
+                    uint16_t* legacy, double* nums, uint32_t capNums, uint32_t* nNums, uint64_t* resumedAt) {
   g_ck = ck;
   g_ckLeaves = ckLeaves;
   g_ckChars = ckChars;
@@ -318,8 +287,8 @@ int emu_huge_resume_adj(const fmt_mt_batch* b, uint32_t d, const uint32_t* ck, c
   g_seedNums = numsIn;
   g_seedNumN = nNumsIn;
   g_resumedAt = 0;
-  const int st = emu_huge_replay_adj(b, d, hdr, leaves, capLeaves, chars, capChars, props, nullptr, 0, nullptr, 0, legacy,
-                                     nums, capNums, nNums);
+  const int st = emu_huge_replay_adj(b, d, hdr, leaves, capLeaves, chars, capChars, props, catchup, capCatchup, rmOrder,
+                                     capRm, legacy, nums, capNums, nNums);
   g_ck = nullptr;
   g_ckLeaves = nullptr;
   g_ckChars = nullptr;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "../../fluidframework_amd/csrc/mt_engine.h"
@@ -396,44 +397,45 @@ int emu_mt_replay(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf
 
 // The large tier over every document from its first op, each document it is about to outgrow
 // stopping with its large → huge checkpoint (hugeCk: fmt_ckpt::kWords words per document; header
-// status fmt_ckpt::kStatusHuge) for emu_huge_resume (results at large strides).
-// Annotate-adjust batches run the large tier's Adj variant (Doc<true, G, false, true>, as the runtime):
-// the legacy views of the documents it finishes via emu_mt_legacy_props, and each document's
-// PropertiesManager records and computed numbers, which the huge tier resumes with, via emu_mt_adj_slab.
+// status fmt_ckpt::kStatusHuge) for emu_huge_resume (results at large strides), for any flag set the
+// runtime accepts (launchMergeTreeLarge's choice of variant): annotate-adjust batches run
+// Doc<true, G, Rm, true>, others Doc<Ob, G, Rm>, with Rm when the batch holds FMT_MT_F_RMORDER ops
+// (rmOrder[n_docs x capRm] then receives the entries, which keep their leaf ids in a stopped document)
+// and catch-up recording beside either (catchup[n_docs x capCatchup], or nullptr). Annotate-adjust
+// batches: the legacy views of the documents the large tier finishes via emu_mt_legacy_props, and each
+// document's PropertiesManager records and computed numbers, which the huge tier resumes with, via
+// emu_mt_adj_slab.
 int emu_mt_replay_large_ckpt(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                             fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup, uint32_t* hugeCk) {
+                             fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
+                             fmt_mt_remove_order* rmOrder, uint32_t capRm, uint32_t* hugeCk) {
+  using G = fmt_mt::LargeTier;
   g_nums.clear();
   g_legacyStride = 0;
-  if (b->adjusts != nullptr) {
-    prepareNumbers(b);
-    using DL = fmt_mt::Doc<true, fmt_mt::LargeTier, false, true>;
-    g_legacyStride = DL::kCapLeaves;
-    g_legacy.assign(static_cast<size_t>(b->n_docs) * g_legacyStride, 0xFFFFu);
-    return replayAll<true, fmt_mt::LargeTier, false, true>(b, headers, leaves, chars, props, catchup, capCatchup, nullptr, 0,
-                                                           nullptr, false, 0, 0, nullptr, nullptr, g_legacy.data(), hugeCk);
+  bool ob = false, rm = false;
+  for (uint64_t i = 0; i < b->n_ops; i++) {
+    ob = ob || b->ops[i].type == FMT_MT_OBLITERATE || b->ops[i].type == FMT_MT_OBLITERATE_SIDED;
+    rm = rm || (b->ops[i].flags & FMT_MT_F_RMORDER) != 0;
   }
-  bool ob = false;
-  for (uint64_t i = 0; i < b->n_ops && !ob; i++) ob = b->ops[i].type == FMT_MT_OBLITERATE || b->ops[i].type == FMT_MT_OBLITERATE_SIDED;
-  using G = fmt_mt::LargeTier;
-  return ob ? replayAll<true, G>(b, headers, leaves, chars, props, catchup, capCatchup, nullptr, 0, nullptr, false, 0, 0,
-                                 nullptr, nullptr, nullptr, hugeCk)
-            : replayAll<false, G>(b, headers, leaves, chars, props, catchup, capCatchup, nullptr, 0, nullptr, false, 0, 0,
-                                  nullptr, nullptr, nullptr, hugeCk);
-}
-
-// As emu_mt_replay_large_ckpt for a batch with remove-order recording (the large tier's Rm variant):
-// rmOrder[n_docs x capRm] receives the entries, which keep their leaf ids in a stopped document.
-int emu_mt_replay_large_ckpt_rm(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                                fmt_mt_propset* props, fmt_mt_remove_order* rmOrder, uint32_t capRm, uint32_t* hugeCk) {
-  g_nums.clear();
-  g_legacyStride = 0;
-  bool ob = false;
-  for (uint64_t i = 0; i < b->n_ops && !ob; i++) ob = b->ops[i].type == FMT_MT_OBLITERATE || b->ops[i].type == FMT_MT_OBLITERATE_SIDED;
-  using G = fmt_mt::LargeTier;
-  return ob ? replayAll<true, G, true>(b, headers, leaves, chars, props, nullptr, 0, rmOrder, capRm, nullptr, false, 0, 0,
-                                       nullptr, nullptr, nullptr, hugeCk)
-            : replayAll<false, G, true>(b, headers, leaves, chars, props, nullptr, 0, rmOrder, capRm, nullptr, false, 0, 0,
-                                        nullptr, nullptr, nullptr, hugeCk);
+  if (rm && rmOrder == nullptr) return FMT_E_DATA;
+  if (!rm) rmOrder = nullptr;
+  uint16_t* legacy = nullptr;
+  const bool adj = b->adjusts != nullptr;
+  if (adj) {
+    prepareNumbers(b);
+    g_legacyStride = fmt_mt::Doc<true, G, false, true>::kCapLeaves;
+    g_legacy.assign(static_cast<size_t>(b->n_docs) * g_legacyStride, 0xFFFFu);
+    legacy = g_legacy.data();
+  }
+  auto go = [&](auto obT, auto rmT, auto adjT) {
+    return replayAll<decltype(obT)::value, G, decltype(rmT)::value, decltype(adjT)::value>(
+        b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, nullptr, false, 0, 0, nullptr, nullptr,
+        legacy, hugeCk);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (adj) return rm ? go(T{}, T{}, T{}) : go(T{}, F{}, T{});
+  if (ob) return rm ? go(T{}, T{}, F{}) : go(T{}, F{}, F{});
+  return rm ? go(F{}, T{}, F{}) : go(F{}, F{}, F{});
 }
 
 uint32_t emu_huge_ckpt_words() { return fmt_ckpt::kWords; }

@@ -44,9 +44,9 @@ def emu_lib():
         L.emu_mt_replay_local.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int]
         L.emu_mt_regen.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                    ctypes.POINTER(ctypes.c_uint32)]
-        L.emu_mt_replay_large_ckpt.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_uint32, ctypes.c_void_p]
+        L.emu_mt_replay_large_ckpt.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                                                       ctypes.c_void_p]
         L.emu_huge_ckpt_words.restype = ctypes.c_uint32
-        L.emu_mt_replay_large_ckpt_rm.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_uint32, ctypes.c_void_p]
         L.emu_mt_adj_slab.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                       ctypes.POINTER(ctypes.c_uint32)]
         _emu = L
@@ -78,24 +78,20 @@ def huge_emu_lib(tiny_groups=False):
         L.emu_huge_replay_adj.argtypes = L.emu_huge_replay_rec.argtypes + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                                           ctypes.c_void_p]
         L.emu_huge_replay_hi.argtypes = L.emu_huge_replay.argtypes + [ctypes.c_void_p]
-        L.emu_huge_resume.argtypes = ([ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6 +
-                                      [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)])
-        L.emu_huge_resume_adj.argtypes = ([ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5 +
-                                          [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)])
-        L.emu_huge_resume_rm.argtypes = ([ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6 +
-                                         [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)])
+        L.emu_huge_resume.argtypes = ([ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5 +
+                                      [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)])
         _huge[tiny_groups] = L
     return _huge[tiny_groups]
 
 
-def emu_huge_replay_adjust(batch, doc=0, tiny_groups=False, cap_props=65534):
-    """(header, leaves, chars, props, legacy prop sets per leaf, computed numbers) of document `doc`
-    of an annotate-adjust batch replayed by the emulated huge engine."""
+def emu_huge_replay_adjust(batch, doc=0, tiny_groups=False, cap_props=65534, cap_rm=0):
+    """(header, leaves, chars, props, legacy prop sets per leaf, computed numbers[, remove-order
+    entries: cap_rm > 0, the Adj x Rm variant]) of document `doc` of an annotate-adjust batch replayed
+    by the emulated huge engine."""
     from fluidframework_amd.native import DOC_RESULT_DTYPE, LEAF_DTYPE, PROPSET_DTYPE, batch_struct
 
     sd = batch.snapshots[doc] if batch.snapshots is not None else None
@@ -109,14 +105,16 @@ def emu_huge_replay_adjust(batch, doc=0, tiny_groups=False, cap_props=65534):
     legacy = np.zeros(cap_leaves, dtype="<u2")
     nums = np.zeros(1 << 16, dtype=np.float64)
     nn = ctypes.c_uint32()
+    rm = np.zeros(max(cap_rm, 1), dtype=RM_ORDER_DTYPE)
     b, keep = batch_struct(batch)
     huge_emu_lib(tiny_groups).emu_huge_replay_adj(ctypes.addressof(b), doc, _p(hdr), _p(leaves), cap_leaves, _p(chars),
-                                                  cap_chars, _p(props), None, 0, None, 0, _p(legacy), _p(nums),
-                                                  len(nums), ctypes.byref(nn))
+                                                  cap_chars, _p(props), None, 0, _p(rm) if cap_rm else None, cap_rm,
+                                                  _p(legacy), _p(nums), len(nums), ctypes.byref(nn))
     del keep
     h = hdr[0]
     n = int(h["n_leaves"])
-    return h, leaves[:n], chars[: int(h["n_chars"])], props[: int(h["n_props"])], legacy[:n], nums[: nn.value]
+    out = h, leaves[:n], chars[: int(h["n_chars"])], props[: int(h["n_props"])], legacy[:n], nums[: nn.value]
+    return out + (rm[: int(h["n_rm_order"])],) if cap_rm else out
 
 
 def emu_huge_replay(batch, doc=0, cap_leaves=None, cap_chars=None, tiny_groups=False, cap_catchup=0, cap_rm=0,
@@ -180,9 +178,11 @@ def emu_huge_replay_hi(batch, doc=0, tiny_groups=False, cap_props=65534, hi2=Fal
 def emu_grow_replay(batch, tiny_groups=False, cap_catchup=0, cap_rm=0):
     """The runtime's large → huge path under host emulation: the large tier over every document from
     its first op, each document it is about to outgrow stopping at its checkpoint (huge_ckpt.h), then
-    the huge tier resuming it from there. Returns per document (header, leaves, chars, props[, catch-up
-    ranges][, remove-order entries: cap_rm > 0][, legacy prop sets per leaf, computed numbers:
-    annotate-adjust batches]) and the op index each resumed at (0: the large tier finished it)."""
+    the huge tier resuming it from there, in the variants the runtime launches for the batch's flag set
+    (catch-up recording, remove-order recording and annotate-adjust in any combination). Returns per
+    document (header, leaves, chars, props[, catch-up ranges: cap_catchup > 0][, remove-order entries:
+    cap_rm > 0][, legacy prop sets per leaf, computed numbers: annotate-adjust batches]) and the op index
+    each resumed at (0: the large tier finished it)."""
     adjust = batch.adjusts is not None
     cl, cc, cp = emu_caps(True)
     n = batch.n_docs
@@ -191,18 +191,13 @@ def emu_grow_replay(batch, tiny_groups=False, cap_catchup=0, cap_rm=0):
     chars = np.zeros(n * cc, dtype="<u2")
     props = np.zeros(n * cp, dtype=PROPSET_DTYPE)
     cu = np.zeros(max(n * cap_catchup, 1), dtype=CATCHUP_DTYPE)
-    L = emu_lib()
-    ck = np.zeros(n * int(L.emu_huge_ckpt_words()), dtype=np.uint32)
-    b, keep = batch_struct(batch)
     rm = np.zeros(max(n * cap_rm, 1), dtype=RM_ORDER_DTYPE)
-    if cap_rm:
-        assert not cap_catchup and not adjust
-        L.emu_mt_replay_large_ckpt_rm(ctypes.addressof(b), _p(hdr), _p(leaves), _p(chars), _p(props), _p(rm), cap_rm,
-                                      _p(ck))
-    else:
-        L.emu_mt_replay_large_ckpt(ctypes.addressof(b), _p(hdr), _p(leaves), _p(chars), _p(props),
-                                   _p(cu) if cap_catchup else None, cap_catchup, _p(ck))
+    L = emu_lib()
     words = int(L.emu_huge_ckpt_words())
+    ck = np.zeros(n * words, dtype=np.uint32)
+    b, keep = batch_struct(batch)
+    L.emu_mt_replay_large_ckpt(ctypes.addressof(b), _p(hdr), _p(leaves), _p(chars), _p(props),
+                               _p(cu) if cap_catchup else None, cap_catchup, _p(rm) if cap_rm else None, cap_rm, _p(ck))
     out, resumed = [], []
     for d in range(n):
         if int(hdr[d]["status"]) != -35:  # (fmt_ckpt::kStatusHuge)
@@ -227,33 +222,25 @@ def emu_grow_replay(batch, tiny_groups=False, cap_catchup=0, cap_rm=0):
         lv = np.zeros(hcl, dtype=LEAF_DTYPE)
         ch = np.zeros(hcc, dtype="<u2")
         pr = np.zeros(65534, dtype=PROPSET_DTYPE)
-        cud = np.zeros(max(cap_catchup, 1), dtype=CATCHUP_DTYPE)
-        if cap_catchup:
-            cud[:cap_catchup] = cu[d * cap_catchup: (d + 1) * cap_catchup]
+        # (in the runtime both tiers write the document's own HBM slabs; the two emulators keep their own)
+        cud = cu[d * cap_catchup: (d + 1) * cap_catchup].copy() if cap_catchup else None
+        rmd = rm[d * cap_rm: (d + 1) * cap_rm].copy() if cap_rm else None
         at = ctypes.c_uint64(0)
+        pm = nums_in = legacy = nums = None
+        pm_recs, n_in, nn = 0, ctypes.c_uint32(0), ctypes.c_uint32(0)
         if adjust:
-            assert not cap_catchup
             pm_recs = int(ck[d * words + 15])  # (fmt_ckpt::kPmN)
             pm = np.zeros(4 * max(pm_recs, 1), dtype=np.uint32)
             nums_in = np.zeros(4096, dtype=np.float64)
-            n_in = ctypes.c_uint32(0)
             assert L.emu_mt_adj_slab(d, _p(pm), pm_recs, _p(nums_in), len(nums_in), ctypes.byref(n_in)) == 0
             legacy = np.zeros(hcl, dtype="<u2")
             nums = np.zeros(1 << 16, dtype=np.float64)
-            nn = ctypes.c_uint32(0)
-            huge_emu_lib(tiny_groups).emu_huge_resume_adj(
-                ctypes.addressof(b), d, _p(ck[d * words:]), _p(leaves[d * cl:]), _p(chars[d * cc:]), _p(props[d * cp:]),
-                _p(pm), pm_recs, _p(nums_in), n_in.value, _p(h1), _p(lv), hcl, _p(ch), hcc, _p(pr), _p(legacy),
-                _p(nums), len(nums), ctypes.byref(nn), ctypes.byref(at))
-        elif cap_rm:
-            rmd = rm[d * cap_rm: (d + 1) * cap_rm].copy()
-            huge_emu_lib(tiny_groups).emu_huge_resume_rm(
-                ctypes.addressof(b), d, _p(ck[d * words:]), _p(leaves[d * cl:]), _p(chars[d * cc:]), _p(props[d * cp:]),
-                _p(h1), _p(lv), hcl, _p(ch), hcc, _p(pr), _p(rmd), cap_rm, ctypes.byref(at))
-        else:
-            huge_emu_lib(tiny_groups).emu_huge_resume(
-                ctypes.addressof(b), d, _p(ck[d * words:]), _p(leaves[d * cl:]), _p(chars[d * cc:]), _p(props[d * cp:]),
-                _p(h1), _p(lv), hcl, _p(ch), hcc, _p(pr), _p(cud) if cap_catchup else None, cap_catchup, ctypes.byref(at))
+        huge_emu_lib(tiny_groups).emu_huge_resume(
+            ctypes.addressof(b), d, _p(ck[d * words:]), _p(leaves[d * cl:]), _p(chars[d * cc:]), _p(props[d * cp:]),
+            _p(pm) if adjust else None, pm_recs, _p(nums_in) if adjust else None, n_in.value, _p(h1), _p(lv), hcl, _p(ch),
+            hcc, _p(pr), _p(cud) if cap_catchup else None, cap_catchup, _p(rmd) if cap_rm else None, cap_rm,
+            _p(legacy) if adjust else None, _p(nums) if adjust else None, len(nums) if adjust else 0, ctypes.byref(nn),
+            ctypes.byref(at))
         h = h1[0]
         res = (h, lv[: int(h["n_leaves"])], ch[: int(h["n_chars"])], pr[: int(h["n_props"])])
         if cap_catchup:

@@ -132,16 +132,15 @@ def test_engine_hand_cases(orc):
         assert np.array_equal(emu_numbers(d), nums[d]), d
 
 
-def adjust_fixture_batch(exact_tail=False, seed=11, narrow=False, messages=False):
-    """The reference's conflict-farm fixtures with every annotate rewritten: adjusts of "n" (and "w")
-    with deltas from {1, -2, 0.5, 0.1, -0.3, 1e-7 …} and sometimes min/max clamps (null ones too), raw
-    numbers on "n", nulls, or the original {"client"} props. With exact_tail, annotates above the
-    document's final minSeq keep their original props (another key), so its legacy summary is exact.
-    With narrow, deltas are ±1 / 2 clamped to [0, 4] (few distinct values: documents fit the small
-    tier's 32 prop sets). With messages, returns [(initial text, messages, final text)] instead."""
-    fx = json.load(gzip.open(GOLDEN, "rt", encoding="utf-8"))
-    rng = random.Random(seed)
-    deltas = [1, -2, 0.5, 0.1, -0.3, 3, 1e-7, -0.25, 7]
+ADJUST_DELTAS = [1, -2, 0.5, 0.1, -0.3, 3, 1e-7, -0.25, 7]
+
+
+def annotate_rewriter(rng, narrow=False):
+    """op -> op: every annotate rewritten (other ops pass through) into adjusts of "n" (and "w") with
+    deltas from ADJUST_DELTAS and sometimes min/max clamps (null ones too), raw numbers on "n", nulls, or
+    {"client"} props; with narrow, deltas of ±1 / 2 clamped to [0, 4] (few distinct values: documents
+    fit the small tier's 32 prop sets). Draws from rng, so the order of calls fixes the result."""
+    deltas = ADJUST_DELTAS
 
     def rewrite(op):
         if op.get("type") != 2:
@@ -173,6 +172,19 @@ def adjust_fixture_batch(exact_tail=False, seed=11, narrow=False, messages=False
             if rng.random() < 0.1:
                 op["props"] = {"n": 2}
         return op
+
+    return rewrite
+
+
+def adjust_fixture_batch(exact_tail=False, seed=11, narrow=False, messages=False):
+    """The reference's conflict-farm fixtures with every annotate rewritten (annotate_rewriter): adjusts
+    of "n" (and "w") with deltas from {1, -2, 0.5, 0.1, -0.3, 1e-7 …} and sometimes min/max clamps (null
+    ones too), raw numbers on "n", nulls, or the original {"client"} props. With exact_tail, annotates
+    above the document's final minSeq keep their original props (another key), so its legacy summary is
+    exact. With narrow, deltas are ±1 / 2 clamped to [0, 4] (few distinct values: documents fit the small
+    tier's 32 prop sets). With messages, returns [(initial text, messages, final text)] instead."""
+    fx = json.load(gzip.open(GOLDEN, "rt", encoding="utf-8"))
+    rewrite = annotate_rewriter(random.Random(seed), narrow)
 
     docs = []
     for f in fx:

@@ -4,11 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fmt.h"
-
-namespace fmt_mt {
-struct AdjustTables;  // mt_engine.h
-struct LocalTables;   // mt_engine.h (f4)
-}
+#include "mt_bind.h"
 
 namespace fmt_kernels {
 
@@ -32,49 +28,7 @@ hipError_t launchMapLww(const fmt_map_op* ops, const uint64_t* offsets, uint32_t
                         fmt_map_slot* out, int* error, int numCUs, hipStream_t stream, uint32_t* scratch);
 
 // ---- merge-tree replay (mergetree.hip)
-struct MtDeviceBatch {
-  const fmt_mt_op* ops;
-  const uint64_t* docOpOffsets;
-  uint32_t nDocs;
-  const uint16_t* text;
-  const uint32_t* docInit;  // (offset, len) per doc or nullptr
-  const uint32_t* propsOff;
-  const uint32_t* propsKv;
-  uint32_t nPropsOps;
-  const uint64_t* catchupOffsets;  // per-doc catch-up slab offsets (nDocs + 1), or nullptr
-  const fmt_mt_snapshot_doc* snapshots;  // per-doc summary loads, or nullptr
-  const fmt_mt_snapshot_seg* snapshotSegs;
-  const uint64_t* rmOrderOffsets;  // per-doc remove-order slab offsets (nDocs + 1), or nullptr
-  const fmt_mt_snapshot_info* snapshotInfo;  // SnapshotV1 merge info per snapshot segment, or nullptr
-  const fmt_mt_stamp* snapshotStamps;
-  uint64_t nSnapshotInfo;
-  const fmt_mt_relpos* relpos;     // relative positions (FMT_MT_F_REL1/REL2 ops), or nullptr
-  uint32_t nRelpos;
-  uint32_t markerKey;              // key id of "markerId", FMT_MT_NO_MARKER if none
-  const fmt_mt::AdjustTables* adj;  // annotate-adjust tables (device memory), nullptr when none
-  const fmt_mt::LocalTables* loc = nullptr;  // f4 local-client slabs (device memory), nullptr when none
-};
-
-struct MtDeviceOut {
-  fmt_mt_doc_result* headers;  // nDocs
-  fmt_mt_leaf* leaves;         // nDocs * capLeaves
-  uint16_t* chars;             // nDocs * capChars
-  fmt_mt_propset* props;       // nDocs * capProps
-  fmt_mt_catchup_range* catchup;  // slabs at catchupOffsets, or nullptr
-  fmt_mt_remove_order* rmOrder;   // slabs at rmOrderOffsets, or nullptr
-  uint32_t* ckpt;                 // plain batches: per-document register-tier checkpoints (one slot each), or nullptr
-  // large tier over a plain batch: the small tier's result slabs, where it left its checkpoints
-  const fmt_mt_leaf* smallLeaves;
-  const uint16_t* smallChars;
-  // annotate-adjust batches: per leaf the prop set of getAtSeq(minSeq) (legacy summaries), at the
-  // leaves slab's stride; nullptr otherwise
-  uint16_t* legacyProps;
-  // large tier over a plain batch: per large-tier slot, its large → huge checkpoint record
-  // (huge_ckpt.h, fmt_ckpt::kWords words), or nullptr
-  uint32_t* hugeCkpt = nullptr;
-  // set by launchMergeTree for the rounds of a plain batch in which documents may step down a tier
-  bool descend = false;
-};
+// MtDeviceBatch / MtDeviceOut, the views a launch takes: mt_bind.h
 // Bytes of one document's tier checkpoint (mt_engine.h Doc::kCkptWords).
 size_t mergeTreeCheckpointBytes();
 

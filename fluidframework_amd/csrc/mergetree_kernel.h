@@ -11,8 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
-#include "mt_engine.h"
+#include "kernels.h"  // (mt_bind.h, and through it mt_engine.h)
 
 namespace fmt_kernels {
 
@@ -31,15 +30,6 @@ static inline int addTuProfile(uint64_t* out, int n, bool reset) {
   }
   return fmt_mt::kPfCount;
 }
-
-// Result slabs: the compact and small tiers share the small tier's per-document strides (a document
-// the compact tier overflows replays again into the same slab); the large tier has its own.
-template <class C>
-struct Slab {
-  static constexpr size_t kLeaves = C::kHbmChars ? 64 * C::kRows : 64 * fmt_mt::SmallTier::kRows;
-  static constexpr size_t kChars = C::kHbmChars ? C::kCapChars : fmt_mt::SmallTier::kCapChars;
-  static constexpr size_t kProps = C::kHbmChars ? C::kPropCap : fmt_mt::SmallTier::kPropCap;
-};
 
 // LDS bytes per wave: batches without obliterates never touch the live-obliterate table at the end
 // of Scratch (1.6 KiB), which is what lets the compact tier hold 4 waves per SIMD (16 × 9312 B).
@@ -73,94 +63,7 @@ __global__ __launch_bounds__(64 * Waves, WavesPerEU) void mergeTreeKernel(MtDevi
     if (i >= count) break;
     const uint32_t d = docList ? docList[i] : i;
     const size_t slot = C::kHbmChars ? i : d;
-    fmt_mt::DocInputs in;
-    in.ops = batch.ops;
-    in.begin = batch.docOpOffsets[d];
-    in.end = batch.docOpOffsets[d + 1];
-    in.text = batch.text;
-    in.initOff = batch.docInit ? batch.docInit[2 * d] : 0u;
-    in.initLen = batch.docInit ? batch.docInit[2 * d + 1] : 0u;
-    in.propsOff = batch.propsOff;
-    in.propsKv = batch.propsKv;
-    in.nPropsOps = batch.nPropsOps;
-    in.relpos = batch.relpos;
-    in.nRelpos = batch.relpos ? batch.nRelpos : 0u;
-    in.markerKey = batch.markerKey;
-    in.adj = batch.adj;
-    in.loc = Loc ? batch.loc : nullptr;
-    in.doc = d;
-    in.infoAll = batch.snapshotInfo;
-    in.stampsAll = batch.snapshotStamps;
-    in.nInfoAll = batch.snapshotInfo ? batch.nSnapshotInfo : 0u;
-    if (batch.snapshots && batch.snapshots[d].loaded) {
-      const fmt_mt_snapshot_doc sd = batch.snapshots[d];
-      in.snapSegs = batch.snapshotSegs + sd.first_seg;
-      in.snapInfo = batch.snapshotInfo ? batch.snapshotInfo + sd.first_seg : nullptr;
-      in.snapStamps = batch.snapshotStamps;
-      in.nHeader = sd.n_header;
-      in.nBody = sd.n_body;
-      in.snapMinSeq = sd.min_seq;
-      in.snapSeq = sd.seq;
-      in.loaded = 1;
-    } else {
-      in.snapSegs = nullptr;
-      in.snapInfo = nullptr;
-      in.snapStamps = nullptr;
-      in.nHeader = in.nBody = 0;
-      in.snapMinSeq = in.snapSeq = 0;
-      in.loaded = 0;
-    }
-    fmt_mt::DocOutputs o;
-    o.header = out.headers + d;
-    o.leaves = out.leaves + slot * Slab<C>::kLeaves;
-    o.chars = out.chars + slot * Slab<C>::kChars;
-    o.props = out.props + slot * Slab<C>::kProps;
-    if (batch.catchupOffsets) {
-      const uint64_t c0 = batch.catchupOffsets[d], c1 = batch.catchupOffsets[d + 1];
-      o.catchup = out.catchup + c0;
-      o.catchupCap = static_cast<uint32_t>(c1 - c0);
-    } else {
-      o.catchup = nullptr;
-      o.catchupCap = 0;
-    }
-    if (Rm && batch.rmOrderOffsets) {
-      const uint64_t r0 = batch.rmOrderOffsets[d], r1 = batch.rmOrderOffsets[d + 1];
-      o.rmOrder = out.rmOrder + r0;
-      o.rmOrderCap = static_cast<uint32_t>(r1 - r0);
-    } else {
-      o.rmOrder = nullptr;
-      o.rmOrderCap = 0;
-    }
-    if (Doc::kSavesCkpt || Doc::kResumesCkpt || (Ob && Doc::kResumesBig)) {  // (large tier: live obliterates)
-      o.ckpt = out.ckpt ? out.ckpt + static_cast<size_t>(d) * Doc::kCkptWords : nullptr;
-      // (a tier that also saves — the compact one — resumes only over an overflow list: over every
-      // document it is the first tier, and the headers hold whatever an earlier run left)
-      // (kCkptDescend: the tier above left it, see launchMergeTree's rounds)
-      const int st = __builtin_amdgcn_readfirstlane(out.headers[d].status);
-      o.ckptResume = Doc::kResumesCkpt && (!Doc::kSavesCkpt || countDev != nullptr) && o.ckpt != nullptr &&
-                     (st == fmt_mt::kCkptEscalate || (!Ob && st == fmt_mt::kCkptDescend));
-      if constexpr (Doc::kDescends) o.descend = out.descend;
-    } else {
-      o.ckpt = nullptr;
-      o.ckptResume = false;
-    }
-    o.bigCkpt = nullptr;
-    o.bigCkptChars = nullptr;
-    o.legacyProps = out.legacyProps ? out.legacyProps + slot * Slab<C>::kLeaves : nullptr;
-    o.hugeCkpt = Doc::kSavesHuge && out.hugeCkpt != nullptr ? out.hugeCkpt + slot * static_cast<size_t>(fmt_ckpt::kWords) : nullptr;
-    if constexpr (Doc::kSavesBig) {  // batches without remove order (out.ckpt set): the small tier's own slabs
-      if (out.ckpt != nullptr) {
-        o.bigCkpt = reinterpret_cast<uint32_t*>(o.leaves);
-        o.bigCkptChars = o.chars;
-      }
-    }
-    if constexpr (Doc::kResumesBig) {
-      if (out.smallLeaves != nullptr) {
-        o.bigCkpt = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(out.smallLeaves + d * Slab<fmt_mt::SmallTier>::kLeaves));
-        o.bigCkptChars = const_cast<uint16_t*>(out.smallChars + d * Slab<fmt_mt::SmallTier>::kChars);
-        o.ckptResume = __builtin_amdgcn_readfirstlane(out.headers[d].status) == fmt_mt::kCkptEscalate;
-      }
-    }
+    FMT_MT_BIND_DOC(Doc, batch, out, d, slot, Slab<C>::kLeaves, Slab<C>::kChars, Slab<C>::kProps, countDev != nullptr, in, o);
     Doc doc;
     doc.s = scratch;
     doc.run(in, o);
@@ -187,15 +90,9 @@ __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* 
   if (countDev != nullptr) nDocs = *countDev;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nDocs; i += gridDim.x * blockDim.x) {
     const uint32_t d = docList ? docList[i] : i;
-    const int st = headers[d].status;
-    if (st == fmt_mt::kCapacityFinal) headers[d].status = FMT_E_CAPACITY;
-    if (st == FMT_E_CAPACITY || st == fmt_mt::kCkptEscalate) {
-      const uint32_t k = atomicAdd(esc, 1u);
-      esc[1 + k] = d;
-    } else if (down != nullptr && st == fmt_mt::kCkptDescend) {
-      const uint32_t k = atomicAdd(down, 1u);
-      down[1 + k] = d;
-    }
+    const HandOff to = collectHeader(headers[d]);
+    uint32_t* list = to == HandOff::kUp ? esc : to == HandOff::kDown ? down : nullptr;
+    if (list != nullptr) list[1 + atomicAdd(list, 1u)] = d;
   }
 }
 #endif

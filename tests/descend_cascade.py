@@ -1,38 +1,16 @@
-"""The plain-batch cascade with stepping down under host emulation (tests/emu/mt_emu_descend.cpp: one
-launch per call, the step-down switch and both lists exposed), the rounds of launchMergeTree
-(csrc/mergetree.hip) driven from here, and the documents the step-down tests are built from. Shared by
-test_descend_emulated.py (CPU) and test_gpu_descend.py (the same batches on the device)."""
+"""The plain-batch cascade with stepping down under host emulation (tests/emu/mt_emu_tiers.cpp through
+micro_cascade.lib(): one launch per call, the step-down switch and both lists exposed), the rounds of
+launchMergeTree (csrc/mergetree.hip) driven from here, and the documents the step-down tests are built
+from. Shared by test_descend_emulated.py (CPU) and test_gpu_descend.py (the same batches on the device)."""
 import ctypes
-import os
 
 import numpy as np
 
 from fluidframework_amd.native import batch_struct
-from micro_cascade import CKPT, COMPACT, E_CAPACITY, LARGE, MICRO, SMALL, Cascade, _msg
-from mt_compare import _build_atomic, _p
+from micro_cascade import CKPT, COMPACT, E_CAPACITY, LARGE, MICRO, SMALL, Cascade, _msg, lib
+from mt_compare import _p
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "_build", "libmt_emu_descend.so")
 ROUNDS = 2  # csrc/mergetree.hip kDescendRounds
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        src = os.path.join(HERE, "emu", "mt_emu_descend.cpp")
-        csrc = os.path.join(HERE, "..", "fluidframework_amd", "csrc")
-        deps = [src, os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(csrc, f) for f in
-                                                                      ("mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
-        if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(d) for d in deps):
-            os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-            _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], LIB_PATH, src)
-        L = ctypes.CDLL(LIB_PATH)
-        L.emu_descend_consts.argtypes = [ctypes.POINTER(ctypes.c_int32)]
-        L.emu_descend_tier.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 +
-                                       [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4)
-        _lib = L
-    return _lib
 
 
 def consts():
@@ -90,9 +68,9 @@ class DescendCascade(Cascade):
             small = (_p(self.leaves), _p(self.chars))
         else:
             lv, ch, pr, small = self.leaves, self.chars, self.props, (None, None)
-        rc = lib().emu_descend_tier(ctypes.addressof(b), tier, _p(self.hdr), _p(lv), _p(ch), _p(pr), cu, self.cap_catchup, ck,
-                                    _p(docs) if docs is not None else None, int(descend), _p(up),
-                                    _p(down) if down is not None else None, small[0], small[1])
+        rc = lib().emu_tier_launch(ctypes.addressof(b), tier, _p(self.hdr), _p(lv), _p(ch), _p(pr), cu, self.cap_catchup, ck,
+                                   _p(docs) if docs is not None else None, int(descend), _p(up),
+                                   _p(down) if down is not None else None, small[0], small[1])
         del keep
         assert rc == len(ids)
         st = self.hdr["status"][ids].copy()

@@ -1,13 +1,14 @@
-// mt_emu.cpp — TEST INFRASTRUCTURE ONLY: the merge-tree engine source (mt_engine.h) compiled for the
-// host with the 64-lane emulation of wave.h, so the CPU parity suite can check the exact kernel
-// logic against the oracle without a GPU. Never loaded by the product (libfmt.so has no CPU path).
+// mt_emu.cpp — TEST INFRASTRUCTURE ONLY: the merge-tree engine source (mt_engine.h) and the launch
+// binding around it (mt_bind.h) compiled for the host with the 64-lane emulation of wave.h, so the CPU
+// parity suite can check the exact kernel logic against the oracle without a GPU. Never loaded by the
+// product (libfmt.so has no CPU path).
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <type_traits>
 #include <vector>
 
-#include "../../fluidframework_amd/csrc/mt_engine.h"
+#include "emu_batch.h"
 
 // Annotate-adjust state of the last emulated replay (the runtime's number slabs, fixed capacity
 // here): the batch's host numbers sorted for number → id lookups, per-document number tables.
@@ -124,76 +125,23 @@ static int replayAll(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_l
   using Doc = fmt_mt::Doc<Ob, C, Rm, Adj, Loc>;
   auto scratch = std::make_unique<fmt_mt::Scratch<C>>();
   auto doc = std::make_unique<Doc>();
+  const EmuBatch eb(b, catchup != nullptr, capCatchup, rmOrder != nullptr, capRm, g_nums.empty() ? nullptr : &g_adj,
+                    Loc ? &g_loc : nullptr);
+  const fmt_kernels::MtDeviceOut out{headers, leaves, chars, props, catchup, rmOrder, ckpt, smallLeaves, smallChars,
+                                     legacy, hugeCk};
+  if (leafStride == 0) leafStride = Doc::kCapLeaves;  // the tier alone, at its own strides
+  if (charStride == 0) charStride = Doc::kCapChars;
   int status = FMT_OK;
   for (uint32_t d = 0; d < b->n_docs; d++) {
     if (onlyEscalated && headers[d].status != FMT_E_CAPACITY && headers[d].status != fmt_mt::kCkptEscalate) continue;
     std::memset(scratch.get(), 0xCD, sizeof(fmt_mt::Scratch<C>));  // poison: state must be initialized
-    fmt_mt::DocInputs in;
-    in.ops = b->ops;
-    in.begin = b->doc_op_offsets[d];
-    in.end = b->doc_op_offsets[d + 1];
-    in.text = b->text;
-    in.initOff = b->doc_init ? b->doc_init[2 * d] : 0u;
-    in.initLen = b->doc_init ? b->doc_init[2 * d + 1] : 0u;
-    in.propsOff = b->props_off;
-    in.propsKv = b->props_kv;
-    in.nPropsOps = b->n_props_ops;
-    in.relpos = b->relpos;
-    in.nRelpos = b->relpos ? b->n_relpos : 0u;
-    in.markerKey = b->marker_id_key;
-    in.adj = g_nums.empty() ? nullptr : &g_adj;
-    in.doc = d;
-    in.loc = Loc ? &g_loc : nullptr;
-    in.infoAll = b->snapshot_info;
-    in.stampsAll = b->snapshot_stamps;
-    in.nInfoAll = b->snapshot_info ? b->n_snapshot_segs : 0u;
-    if (b->snapshots && b->snapshots[d].loaded) {
-      const fmt_mt_snapshot_doc sd = b->snapshots[d];
-      in.snapSegs = b->snapshot_segs + sd.first_seg;
-      in.snapInfo = b->snapshot_info ? b->snapshot_info + sd.first_seg : nullptr;
-      in.snapStamps = b->snapshot_stamps;
-      in.nHeader = sd.n_header;
-      in.nBody = sd.n_body;
-      in.snapMinSeq = sd.min_seq;
-      in.snapSeq = sd.seq;
-      in.loaded = 1;
-    } else {
-      in.snapSegs = nullptr;
-      in.snapInfo = nullptr;
-      in.snapStamps = nullptr;
-      in.nHeader = in.nBody = 0;
-      in.snapMinSeq = in.snapSeq = 0;
-      in.loaded = 0;
-    }
-    fmt_mt::DocOutputs o;
-    o.header = headers + d;
-    o.leaves = leaves + static_cast<size_t>(d) * (leafStride ? leafStride : Doc::kCapLeaves);
-    o.chars = chars + static_cast<size_t>(d) * (charStride ? charStride : Doc::kCapChars);
-    o.props = props + static_cast<size_t>(d) * Doc::kPropCap;
-    o.catchup = catchup ? catchup + static_cast<size_t>(d) * capCatchup : nullptr;
-    o.catchupCap = catchup ? capCatchup : 0u;
-    o.rmOrder = rmOrder ? rmOrder + static_cast<size_t>(d) * capRm : nullptr;
-    o.rmOrderCap = rmOrder ? capRm : 0u;
-    o.ckpt = ckpt && (Doc::kSavesCkpt || Doc::kResumesCkpt || (Ob && Doc::kResumesBig))
-                 ? ckpt + static_cast<size_t>(d) * Doc::kCkptWords : nullptr;
-    o.ckptResume = o.ckpt != nullptr && Doc::kResumesCkpt && headers[d].status == fmt_mt::kCkptEscalate;
-    o.bigCkpt = nullptr;
-    o.bigCkptChars = nullptr;
-    o.legacyProps = legacy ? legacy + static_cast<size_t>(d) * (leafStride ? leafStride : Doc::kCapLeaves) : nullptr;
-    o.hugeCkpt = Doc::kSavesHuge && hugeCk != nullptr ? hugeCk + static_cast<size_t>(d) * fmt_ckpt::kWords : nullptr;
-    if (Doc::kSavesBig && ckpt != nullptr) {  // the small tier of a cascade: its own slabs
-      o.bigCkpt = reinterpret_cast<uint32_t*>(o.leaves);
-      o.bigCkptChars = o.chars;
-    }
-    if (Doc::kResumesBig && smallLeaves != nullptr) {
-      o.bigCkpt = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(smallLeaves + static_cast<size_t>(d) * 512));
-      o.bigCkptChars = const_cast<uint16_t*>(smallChars + static_cast<size_t>(d) * fmt_mt::SmallTier::kCapChars);
-      o.ckptResume = headers[d].status == fmt_mt::kCkptEscalate;
-    }
+    // (onlyEscalated: what a launch over the overflow list replays)
+    const fmt_kernels::DocBinding bd =
+        fmt_kernels::bindDoc<Doc>(eb.view, out, d, d, leafStride, charStride, Doc::kPropCap, onlyEscalated);
     new (doc.get()) Doc();
     doc->s = scratch.get();
-    doc->run(in, o);
-    if (headers[d].status == fmt_mt::kCapacityFinal) headers[d].status = FMT_E_CAPACITY;  // as collectOverflowKernel
+    doc->run(bd.in, bd.o);
+    (void)fmt_kernels::collectHeader(headers[d]);  // (kCapacityFinal → FMT_E_CAPACITY; no lists here)
     if (headers[d].status == fmt_mt::kCkptEscalate) continue;  // the small tier resumes it
     if (headers[d].status == fmt_ckpt::kStatusHuge) continue;  // the huge tier resumes it
     if (headers[d].status != FMT_OK && status == FMT_OK) status = headers[d].status;

@@ -1,6 +1,8 @@
-"""The plain-batch tier cascade micro → compact → small → large under host emulation, one tier per
-call (tests/emu/mt_emu_micro.cpp), and the documents the micro-tier tests are built from. Shared by
-test_micro_tier_emulated.py (CPU) and test_gpu_micro_tier.py (the same batches on the device)."""
+"""The plain-batch tier cascade micro → compact → small → large under host emulation, one launch per
+call (tests/emu/mt_emu_tiers.cpp: the engine and the kernel's own launch binding, csrc/mt_bind.h,
+compiled for the host), and the documents the micro-tier tests are built from. Shared by
+test_micro_tier_emulated.py (CPU) and test_gpu_micro_tier.py (the same batches on the device); lib() is
+also what descend_cascade.py drives."""
 import ctypes
 import os
 
@@ -10,7 +12,7 @@ from fluidframework_amd.native import CATCHUP_DTYPE, DOC_RESULT_DTYPE, LEAF_DTYP
 from mt_compare import _build_atomic, _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "_build", "libmt_emu_micro.so")
+LIB_PATH = os.path.join(HERE, "_build", "libmt_emu_tiers.so")
 MICRO, COMPACT, SMALL, LARGE = 0, 1, 2, 3
 OK, E_CAPACITY, CKPT = 0, -3, -34  # header statuses (CKPT: fmt_mt::kCkptEscalate, stopped at a checkpoint)
 _lib = None
@@ -19,10 +21,10 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        src = os.path.join(HERE, "emu", "mt_emu_micro.cpp")
+        src = os.path.join(HERE, "emu", "mt_emu_tiers.cpp")
         csrc = os.path.join(HERE, "..", "fluidframework_amd", "csrc")
-        deps = [src, os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(csrc, f) for f in
-                                                                      ("mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
+        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + \
+               [os.path.join(csrc, f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
         if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
             _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], LIB_PATH, src)
@@ -30,8 +32,11 @@ def lib():
         L.emu_micro_ckpt_words.restype = ctypes.c_uint32
         L.emu_micro_ckpt_layout.argtypes = [ctypes.POINTER(ctypes.c_uint32)] * 4
         L.emu_micro_caps.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_uint32)] * 2
-        L.emu_micro_tier.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 +
-                                     [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p])
+        L.emu_descend_consts.argtypes = [ctypes.POINTER(ctypes.c_int32)]
+        L.emu_tier_launch.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 +
+                                      [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4)
+        L.emu_bind_resumes.argtypes = [ctypes.c_int] * 6
+        L.emu_bind_collect.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
         _lib = L
     return _lib
 
@@ -72,6 +77,10 @@ class Cascade:
         """One tier: the micro tier over every document, any other over the documents the tier before
         it left (checkpointed or overflowed). Returns the statuses after it."""
         only = tier != MICRO if only_escalated is None else only_escalated
+        docs = None  # the overflow list a launch before this one built: [0] = n, then ids in document order
+        if only:
+            ids = np.nonzero(np.isin(self.hdr["status"], (E_CAPACITY, CKPT)))[0]
+            docs = np.concatenate(([len(ids)], ids)).astype(np.uint32)
         b, keep = batch_struct(self.batch)
         cu = _p(self.cu) if self.cap_catchup else None
         ck = _p(self.ck) if self.ck is not None else None
@@ -81,11 +90,11 @@ class Cascade:
                 self.big = (np.zeros(self.n * self.bl, dtype=LEAF_DTYPE), np.zeros(self.n * self.bc, dtype="<u2"),
                             np.zeros(self.n * self.bp, dtype=PROPSET_DTYPE))
             lv, ch, pr = self.big
-            rc = lib().emu_micro_tier(ctypes.addressof(b), tier, _p(self.hdr), _p(lv), _p(ch), _p(pr), cu, self.cap_catchup,
-                                      ck, int(only), _p(self.leaves), _p(self.chars))
+            small = (_p(self.leaves), _p(self.chars))
         else:
-            rc = lib().emu_micro_tier(ctypes.addressof(b), tier, _p(self.hdr), _p(self.leaves), _p(self.chars),
-                                      _p(self.props), cu, self.cap_catchup, ck, int(only), None, None)
+            lv, ch, pr, small = self.leaves, self.chars, self.props, (None, None)
+        rc = lib().emu_tier_launch(ctypes.addressof(b), tier, _p(self.hdr), _p(lv), _p(ch), _p(pr), cu, self.cap_catchup, ck,
+                                   _p(docs) if docs is not None else None, 0, None, None, small[0], small[1])
         del keep
         assert rc >= 0
         st = self.hdr["status"]

@@ -31,7 +31,7 @@ def emu_lib():
     global _emu
     if _emu is None:
         src = os.path.join(HERE, "emu", "mt_emu.cpp")
-        deps = [src, os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
+        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
         if not os.path.exists(EMU_PATH) or os.path.getmtime(EMU_PATH) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(EMU_PATH), exist_ok=True)
             _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], EMU_PATH, src)

@@ -56,6 +56,27 @@ struct SumDocOut {
 hipError_t launchSummaryRuns(const fmt_mt_doc_result* hdrs, const SumView* views, uint32_t nDocs, SumRun* runs,
                              uint16_t* text, unsigned long long* cursors, SumDocOut* docOut, int numCUs,
                              hipStream_t stream);
+// Bulk SnapshotV1 summaries (summary_v1.hip): one record per summary segment, a merged run of acked
+// leaves or one leaf above minSeq with its merge info (snapshotV1.ts:170-276). 32 bytes.
+constexpr uint16_t kV1Marker = 1;   // a Marker (its one unit is the refType)
+constexpr uint16_t kV1Solo = 2;     // one leaf, written with merge info ({"json": ...})
+constexpr uint16_t kV1Removed = 4;  // a solo leaf that is removed: rm_* hold its first remove stamp
+struct SumV1Seg {
+  uint32_t len;        // UTF-16 units
+  uint16_t props;      // prop set id of its head leaf (0xffff: undefined)
+  uint16_t flags;      // kV1*
+  uint32_t leaf;       // solo: the leaf's index (its later stamps are the remove-order entries naming it)
+  int32_t ins_seq;     // solo: the insert stamp
+  int32_t ins_client;
+  int32_t rm_client;   // kV1Removed: the first remove stamp, from the op whose seq is the leaf's rm_seq
+  int32_t rm_seq;
+  uint32_t rm_kind;    // FMT_MT_RM_SET / FMT_MT_RM_SLICE
+};
+// ops / opOffs: the batch's resident op records (the first remover of a leaf is looked up there).
+// Segments, text and per-document spans as launchSummaryRuns writes them (SumDocOut.n_runs: segments).
+hipError_t launchSummaryV1(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_mt_op* ops,
+                           const uint64_t* opOffs, uint32_t nDocs, SumV1Seg* segs, uint16_t* text,
+                           unsigned long long* cursors, SumDocOut* docOut, int numCUs, hipStream_t stream);
 // Packing before a D2H copy (transfer.hip): span i's `words` dwords from src to dst + dstWord.
 struct GatherSpan {
   const uint32_t* src;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/fmt.h"
+#include "../../include/fmt_v1.h"
 #include "huge_engine.h"
 #include "jsnum.h"
 #include "mt_engine.h"  // fmt_mt::AdjustTables
@@ -262,6 +263,15 @@ struct fmt_ctx {
   uint64_t mtNOps = 0, mtTextLen = 0, mtInsertChars = 0, mtInitChars = 0;
   uint32_t mtDocs = 0, mtNProps = 0;
   bool mtHasInit = false, mtLoaded = false;
+  bool mtRan = false;                         // fmt_mt_run completed for the loaded batch
+  // bulk SnapshotV1 summaries (fmt_mt_summarize_v1): the kernel's segments, the remove-order entries,
+  // host blobs (the text, spans and prop sets go through the legacy path's transient buffers)
+  DevBuf<fmt_kernels::SumV1Seg> v1Segs;
+  PinnedBuf<fmt_kernels::SumV1Seg> v1HostSegs;
+  PinnedBuf<fmt_mt_remove_order> v1HostRm;
+  std::vector<std::string> v1Blobs;           // per document: header, then body_0, body_1, ...
+  std::vector<std::vector<uint64_t>> v1Ends;  // per document: where each of those blobs ends in v1Blobs[d]
+  std::vector<int32_t> v1Status;
 };
 
 namespace {
@@ -480,6 +490,7 @@ void fmt_close(fmt_ctx* c) {
   c->spans.release();
   c->packed.release();
   c->digests.release();
+  c->v1Segs.release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -1251,6 +1262,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     FMT_HIP(c, hipStreamSynchronize(c->stream));  // (sv / si / T are about to go out of scope)
   }
   c->mtLocal = local;
+  c->mtRan = false;
   c->mtHiClients = hiClients;
   if (local) {
     // Per-document slabs, sized from the document's local records (a document that needs more reports
@@ -1655,6 +1667,7 @@ int fmt_mt_run(fmt_ctx* c) {
   // compact + small tier (no remove-order recording) or small tier alone, then the large tier when it ran
   // (+1: the huge-tier pass over documents that outgrew the large tier, after the timed events)
   c->stats.launches = (!c->mtHasRmOrder ? 2 : 1) + (nEsc > 0 ? 1 : 0) + (c->mtGrown > 0 ? 1 : 0);
+  c->mtRan = true;
   return FMT_OK;
 }
 
@@ -1801,6 +1814,46 @@ void propsObject(std::string& o, const fmt_mt_propset* ps, const SumDict& D, con
   o.push_back('}');
 }
 
+// toJSONObject of a summary segment: a TextSegment's text or {text, props} (textSegment.ts:62-66), a
+// Marker's {marker: {refType}, props?} (mergeTreeNodes.ts:514-518; its one unit is the refType).
+// propsId: the segment's prop set in `props` (0xffff: undefined; an empty set writes no props either).
+void segmentJson(std::string& out, const uint16_t* text, uint32_t len, uint32_t propsId, bool marker,
+                 const fmt_mt_propset* props, const SumDict& D, const std::vector<double>* nums, uint32_t valueBase) {
+  const bool hasProps = propsId != 0xFFFFu && props[propsId].n > 0;
+  if (marker) {  // Marker.toJSONObject
+    out += "{\"marker\":{\"refType\":" + std::to_string(text[0]) + "}";
+    if (hasProps) {
+      out += ",\"props\":";
+      propsObject(out, props + propsId, D, nums, valueBase);
+    }
+    out.push_back('}');
+  } else if (hasProps) {
+    out += "{\"text\":";
+    jsonQuote16(out, text, len);
+    out += ",\"props\":";
+    propsObject(out, props + propsId, D, nums, valueBase);
+    out.push_back('}');
+  } else {
+    jsonQuote16(out, text, len);
+  }
+}
+
+// Prop set p (0xffff: none) lies within the document's nProps records, and its key / value ids within
+// the tables passed in (value id v names values[vBase + v] below vEnd, or a computed number).
+bool propSetInTables(const fmt_mt_propset* props, uint32_t nProps, uint32_t p, uint32_t nKeys, uint32_t vBase,
+                     uint64_t vEnd, const std::vector<double>* nums) {
+  if (p == 0xFFFFu) return true;
+  const uint32_t pn = p < nProps ? props[p].n : 0u;
+  if (p >= nProps || pn > FMT_MT_PROPS_KEYS_MAX || (pn > 0 && p + (pn - 1) / FMT_MT_PROPS_MAX >= nProps)) return false;
+  for (uint32_t k = 0; k < pn; k++) {
+    const uint32_t kv = props[p + k / FMT_MT_PROPS_MAX].kv[k % FMT_MT_PROPS_MAX];
+    const uint32_t v = kv & 0xFFFFu;
+    const bool computed = nums != nullptr && v >= FMT_MT_VALUE_COMPUTED && v - FMT_MT_VALUE_COMPUTED < nums->size();
+    if ((kv >> 16) >= nKeys || (vBase + static_cast<uint64_t>(v) >= vEnd && !computed)) return false;
+  }
+  return true;
+}
+
 // SnapshotLegacy.emit for one document (snapshotlegacy.ts:161-190 + snapshotChunks.ts:85-204):
 // the header chunk (runs until >= chunk units) and, when runs remain, the body chunk.
 void legacyBlobs(std::string& out, uint32_t* split, const fmt_kernels::SumRun* runs, uint32_t nRuns,
@@ -1821,23 +1874,7 @@ void legacyBlobs(std::string& out, uint32_t* split, const fmt_kernels::SumRun* r
     for (uint32_t i = s0; i < s0 + n; i++) {
       if (i > s0) out.push_back(',');
       const fmt_kernels::SumRun& r = runs[i];
-      const bool hasProps = r.props != 0xFFFFu && props[r.props].n > 0;
-      if (r.flags & 1u) {  // Marker.toJSONObject
-        out += "{\"marker\":{\"refType\":" + std::to_string(text[start[i]]) + "}";
-        if (hasProps) {
-          out += ",\"props\":";
-          propsObject(out, props + r.props, D, nums, valueBase);
-        }
-        out.push_back('}');
-      } else if (hasProps) {
-        out += "{\"text\":";
-        jsonQuote16(out, text + start[i], r.len);
-        out += ",\"props\":";
-        propsObject(out, props + r.props, D, nums, valueBase);
-        out.push_back('}');
-      } else {
-        jsonQuote16(out, text + start[i], r.len);
-      }
+      segmentJson(out, text + start[i], r.len, r.props, (r.flags & 1u) != 0, props, D, nums, valueBase);
     }
     out.push_back(']');
     if (header) {
@@ -1853,6 +1890,123 @@ void legacyBlobs(std::string& out, uint32_t* split, const fmt_kernels::SumRun* r
   emit(0, chunk, true, &n1);
   *split = static_cast<uint32_t>(out.size());
   if (n1 < nRuns) emit(n1, total, false, &n2);
+}
+
+// SnapshotV1.emit for one document (snapshotV1.ts:126-168) over the kernel's segments (extractSync,
+// snapshotV1.ts:170-276): out holds the header blob, then body_0, body_1, ...; ends[k] is where blob k
+// ends. A chunk takes segments until it holds >= chunk units (do ... while: the header always exists).
+// rm: the document's remove-order entries, the later stamps of its removed leaves; names[k]: the
+// JSON-quoted long id of short client k. FMT_E_USAGE when a stamp's client has no name.
+int v1Blobs(std::string& out, std::vector<uint64_t>& ends, const fmt_kernels::SumV1Seg* segs, uint32_t nSegs,
+            const uint16_t* text, const fmt_mt_propset* props, const fmt_mt_remove_order* rm, uint32_t nRm,
+            const char* const* names, uint64_t nNames, int32_t minSeq, int32_t curSeq, uint32_t chunk, const SumDict& D,
+            const std::vector<double>* nums, uint32_t valueBase) {
+  // later stamps bucketed by leaf, each bucket in seq order (stamps.ts:144-158 keeps remote stamps so)
+  std::vector<fmt_mt_remove_order> later;
+  later.reserve(nRm);
+  for (uint32_t i = 0; i < nRm; i++)
+    if (rm[i].leaf != FMT_MT_LEAF_GONE) later.push_back(rm[i]);
+  std::stable_sort(later.begin(), later.end(), [](const fmt_mt_remove_order& a, const fmt_mt_remove_order& b) {
+    return a.leaf != b.leaf ? a.leaf < b.leaf : a.seq < b.seq;
+  });
+  struct Chunk {
+    uint32_t start, count;
+    uint64_t length;
+  };
+  std::vector<Chunk> chunks;
+  uint64_t total = 0;
+  for (uint32_t s0 = 0;;) {
+    uint32_t n = 0;
+    uint64_t len = 0;
+    while (len < chunk && s0 + n < nSegs) len += segs[s0 + n++].len;
+    chunks.push_back({s0, n, len});
+    total += len;
+    s0 += n;
+    if (s0 >= nSegs) break;
+  }
+  bool noName = false;
+  auto name = [&](int32_t client) {
+    if (client < 0 || static_cast<uint64_t>(client) >= nNames) noName = true;
+    else out += names[client];
+  };
+  std::vector<fmt_mt_remove_order> stamps;
+  uint64_t tpos = 0;
+  for (size_t k = 0; k < chunks.size(); k++) {
+    const Chunk& ch = chunks[k];
+    out += "{\"version\":\"1\",\"segmentCount\":" + std::to_string(ch.count) + ",\"length\":" + std::to_string(ch.length) +
+           ",\"segments\":[";
+    for (uint32_t i = ch.start; i < ch.start + ch.count; i++) {
+      if (i > ch.start) out.push_back(',');
+      const fmt_kernels::SumV1Seg& s = segs[i];
+      const bool solo = (s.flags & fmt_kernels::kV1Solo) != 0;
+      if (solo) out += "{\"json\":";
+      segmentJson(out, text + tpos, s.len, s.props, (s.flags & fmt_kernels::kV1Marker) != 0, props, D, nums, valueBase);
+      tpos += s.len;
+      if (!solo) continue;
+      if (s.ins_seq > minSeq) {  // snapshotV1.ts:226-233
+        out += ",\"seq\":" + std::to_string(s.ins_seq) + ",\"client\":";
+        name(s.ins_client);
+      }
+      if (s.flags & fmt_kernels::kV1Removed) {
+        stamps.clear();
+        stamps.push_back({s.leaf, s.rm_client, s.rm_seq, s.rm_kind});
+        auto it = std::lower_bound(later.begin(), later.end(), s.leaf,
+                                   [](const fmt_mt_remove_order& e, uint32_t leaf) { return e.leaf < leaf; });
+        for (; it != later.end() && it->leaf == s.leaf; ++it) stamps.push_back(*it);
+        // setRemove stamps (snapshotV1.ts:235-250), then sliceRemove stamps, "moves" in this format (:252-264)
+        for (uint32_t kind : {static_cast<uint32_t>(FMT_MT_RM_SET), static_cast<uint32_t>(FMT_MT_RM_SLICE)}) {
+          const fmt_mt_remove_order* first = nullptr;
+          for (const auto& st : stamps)
+            if (st.kind == kind) {
+              first = &st;
+              break;
+            }
+          if (first == nullptr) continue;
+          if (kind == FMT_MT_RM_SET) {
+            out += ",\"removedSeq\":" + std::to_string(first->seq) + ",\"removedClient\":";
+            name(first->client);
+            out += ",\"removedClientIds\":[";
+          } else {
+            out += ",\"movedSeq\":" + std::to_string(first->seq) + ",\"movedSeqs\":[";
+            bool sep = false;
+            for (const auto& st : stamps)
+              if (st.kind == kind) {
+                if (sep) out.push_back(',');
+                sep = true;
+                out += std::to_string(st.seq);
+              }
+            out += "],\"movedClientIds\":[";
+          }
+          bool sep = false;
+          for (const auto& st : stamps)
+            if (st.kind == kind) {
+              if (sep) out.push_back(',');
+              sep = true;
+              name(st.client);
+            }
+          out.push_back(']');
+        }
+      }
+      out.push_back('}');
+    }
+    out += "],\"startIndex\":" + std::to_string(ch.start);
+    if (k == 0) {
+      out += ",\"headerMetadata\":{\"minSequenceNumber\":" + std::to_string(minSeq) + ",\"sequenceNumber\":" +
+             std::to_string(curSeq) + ",\"orderedChunkMetadata\":[{\"id\":\"header\"}";
+      for (size_t b = 0; b + 1 < chunks.size(); b++) out += ",{\"id\":\"body_" + std::to_string(b) + "\"}";
+      out += "],\"totalLength\":" + std::to_string(total) + ",\"totalSegmentCount\":" + std::to_string(nSegs) + "}";
+    }
+    out.push_back('}');
+    ends.push_back(out.size());
+  }
+  return noName ? FMT_E_USAGE : FMT_OK;
+}
+
+void makeDict(SumDict& D, const char* const* keys, uint32_t nKeys, const char* const* values, uint32_t nValues) {
+  D.keys.assign(keys, keys + nKeys);
+  D.values.assign(values, values + nValues);
+  D.keyIndex.resize(nKeys);
+  for (uint32_t k = 0; k < nKeys; k++) D.keyIndex[k] = arrayIndexOfQuoted(D.keys[k]);
 }
 
 // Where each document's converged state lives: the small tier's slabs, a large-tier slab, or a
@@ -1983,10 +2137,7 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
   const auto t1 = clk::now();
   // format on host threads
   SumDict D;
-  D.keys.assign(keys, keys + nKeys);
-  D.values.assign(values, values + nValues);
-  D.keyIndex.resize(nKeys);
-  for (uint32_t k = 0; k < nKeys; k++) D.keyIndex[k] = arrayIndexOfQuoted(D.keys[k]);
+  makeDict(D, keys, nKeys, values, nValues);
   c->sumBlobs.assign(nd, std::string());
   c->sumSplit.assign(nd, 0);
   c->sumStatus.assign(nd, FMT_OK);
@@ -2006,21 +2157,8 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
         const uint64_t vEnd = c->mtValueBaseHost.empty() ? nValues : std::min<uint64_t>(nValues, c->mtValueBaseHost[d + 1] + 1ull);
         // every prop set a run names, and every key / value id in it, within the tables passed in
         bool bad = false;
-        for (uint32_t i = 0; i < o.n_runs && !bad; i++) {
-          const uint32_t p = runs[o.run_off + i].props;
-          if (p == 0xFFFFu) continue;
-          const uint32_t pn = p < hdr[d].n_props ? propsHost[d][p].n : 0u;
-          if (p >= hdr[d].n_props || pn > FMT_MT_PROPS_KEYS_MAX || (pn > 0 && p + (pn - 1) / FMT_MT_PROPS_MAX >= hdr[d].n_props)) {
-            bad = true;
-            break;
-          }
-          for (uint32_t k = 0; k < pn; k++) {
-            const uint32_t kv = propsHost[d][p + k / FMT_MT_PROPS_MAX].kv[k % FMT_MT_PROPS_MAX];
-            const uint32_t v = kv & 0xFFFFu;
-            const bool computed = nums != nullptr && v >= FMT_MT_VALUE_COMPUTED && v - FMT_MT_VALUE_COMPUTED < nums->size();
-            if ((kv >> 16) >= nKeys || (vBase + static_cast<uint64_t>(v) >= vEnd && !computed)) bad = true;
-          }
-        }
+        for (uint32_t i = 0; i < o.n_runs && !bad; i++)
+          bad = !propSetInTables(propsHost[d], hdr[d].n_props, runs[o.run_off + i].props, nKeys, vBase, vEnd, nums);
         if (bad) {
           c->sumStatus[d] = FMT_E_DATA;
           continue;
@@ -2054,6 +2192,175 @@ int fmt_mt_summary_blobs(fmt_ctx* c, uint32_t doc, const char** header, size_t* 
   if (headerLen) *headerLen = split;
   if (body) *body = b.data() + split;
   if (bodyLen) *bodyLen = b.size() - split;
+  return FMT_OK;
+}
+
+int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, const char* const* values, uint32_t nValues,
+                        const char* const* clientNames, const uint64_t* docClientOffs, uint32_t chunk, uint32_t threads,
+                        fmt_summary_timing* timing) {
+  if (c == nullptr || !c->mtLoaded || !c->mtRan || (nKeys && keys == nullptr) || (nValues && values == nullptr) ||
+      docClientOffs == nullptr || (docClientOffs[c->mtDocs] && clientNames == nullptr))
+    return setErr(c, FMT_E_USAGE, "fmt_mt_summarize_v1: bad arguments, or no fmt_mt_run since the load");
+  if (c->mtLocal)
+    return setErr(c, FMT_E_UNSUPPORTED, "fmt_mt_summarize_v1: the batch holds local-client records (pending stamps have no SnapshotV1 form)");
+  using clk = std::chrono::steady_clock;
+  FMT_HIP(c, hipSetDevice(c->device));
+  const uint32_t nd = c->mtDocs;
+  std::vector<fmt_mt_doc_result> hdr(nd);
+  FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<fmt_kernels::SumView> views;
+  docViews(c, views);
+  uint64_t capSegs = 0, capText = 0;
+  for (uint32_t d = 0; d < nd; d++) {
+    capSegs += hdr[d].n_leaves;
+    capText += hdr[d].n_chars;
+  }
+  FMT_HIP(c, c->sumViews.reserve(nd));
+  FMT_HIP(c, c->v1Segs.reserve(capSegs));
+  FMT_HIP(c, c->sumText.reserve(capText));
+  FMT_HIP(c, c->sumCursors.reserve(2));
+  FMT_HIP(c, c->sumDocs.reserve(nd));
+  FMT_HIP(c, hipMemcpyAsync(c->sumViews.p, views.data(), nd * sizeof(fmt_kernels::SumView), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipMemsetAsync(c->sumCursors.p, 0, 2 * sizeof(unsigned long long), c->stream));
+  FMT_HIP(c, hipEventRecord(c->evS0, c->stream));
+  FMT_HIP(c, fmt_kernels::launchSummaryV1(c->mtHdr.p, c->sumViews.p, c->mtOps.p, c->mtOffs.p, nd, c->v1Segs.p, c->sumText.p,
+                                          c->sumCursors.p, c->sumDocs.p, c->numCUs, c->stream));
+  FMT_HIP(c, hipEventRecord(c->evS1, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  float kms = 0.f;
+  FMT_HIP(c, hipEventElapsedTime(&kms, c->evS0, c->evS1));
+  // fetch: spans, segments, text, and the prop sets and used remove-order prefixes of every document
+  // that replayed, packed on the device (gatherSpansKernel) and brought over in one copy each
+  const auto t0 = clk::now();
+  unsigned long long cur[2];
+  FMT_HIP(c, hipMemcpy(cur, c->sumCursors.p, sizeof cur, hipMemcpyDeviceToHost));
+  constexpr uint32_t kPW = sizeof(fmt_mt_propset) / 4, kRW = sizeof(fmt_mt_remove_order) / 4;
+  std::vector<uint64_t> propOff(nd + 1ull, 0), rmOff(nd + 1ull, 0);
+  for (uint32_t d = 0; d < nd; d++) {
+    const bool ok = hdr[d].status == FMT_OK;
+    const uint64_t slab = c->mtHasRmOrder ? c->mtRmOffsHost[d + 1] - c->mtRmOffsHost[d] : 0;
+    propOff[d + 1] = propOff[d] + (ok ? hdr[d].n_props : 0u);
+    rmOff[d + 1] = rmOff[d] + (ok ? std::min<uint64_t>(hdr[d].n_rm_order, slab) : 0u);
+  }
+  std::vector<fmt_kernels::GatherSpan> sp;
+  for (uint32_t d = 0; d < nd; d++) {
+    if (propOff[d + 1] > propOff[d])
+      sp.push_back({reinterpret_cast<const uint32_t*>(views[d].props), propOff[d] * kPW,
+                    static_cast<uint32_t>(propOff[d + 1] - propOff[d]) * kPW, 0u});
+    if (rmOff[d + 1] > rmOff[d])
+      sp.push_back({reinterpret_cast<const uint32_t*>(c->mtRmOrder.p + c->mtRmOffsHost[d]), propOff[nd] * kPW + rmOff[d] * kRW,
+                    static_cast<uint32_t>(rmOff[d + 1] - rmOff[d]) * kRW, 0u});
+  }
+  if (!sp.empty()) {
+    FMT_HIP(c, c->spans.reserve(sp.size()));
+    FMT_HIP(c, c->packed.reserve(propOff[nd] * kPW + rmOff[nd] * kRW));
+    FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
+                              c->stream));
+    FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
+  }
+  FMT_HIP(c, c->sumHostDocs.reserve(nd));
+  FMT_HIP(c, c->v1HostSegs.reserve(cur[0]));
+  FMT_HIP(c, c->sumHostText.reserve(cur[1]));
+  FMT_HIP(c, c->sumHostProps.reserve(propOff[nd] + 1));
+  FMT_HIP(c, c->v1HostRm.reserve(rmOff[nd] + 1));
+  FMT_HIP(c, hipMemcpyAsync(c->sumHostDocs.p, c->sumDocs.p, nd * sizeof(fmt_kernels::SumDocOut), hipMemcpyDeviceToHost, c->stream));
+  if (cur[0])
+    FMT_HIP(c, hipMemcpyAsync(c->v1HostSegs.p, c->v1Segs.p, cur[0] * sizeof(fmt_kernels::SumV1Seg), hipMemcpyDeviceToHost, c->stream));
+  if (cur[1])
+    FMT_HIP(c, hipMemcpyAsync(c->sumHostText.p, c->sumText.p, cur[1] * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  if (propOff[nd])
+    FMT_HIP(c, hipMemcpyAsync(c->sumHostProps.p, c->packed.p, propOff[nd] * sizeof(fmt_mt_propset), hipMemcpyDeviceToHost,
+                              c->stream));
+  if (rmOff[nd])
+    FMT_HIP(c, hipMemcpyAsync(c->v1HostRm.p, c->packed.p + propOff[nd] * kPW, rmOff[nd] * sizeof(fmt_mt_remove_order),
+                              hipMemcpyDeviceToHost, c->stream));
+  std::vector<std::vector<double>> docNums(c->mtHasAdjust ? nd : 0);
+  if (c->mtHasAdjust) {  // computed annotate-adjust numbers of the documents that have any
+    std::vector<uint32_t> cnt(nd);
+    FMT_HIP(c, hipMemcpyAsync(cnt.data(), c->mtNumCount.p, nd * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint32_t d = 0; d < nd; d++) {
+      docNums[d].resize(cnt[d]);
+      if (cnt[d])
+        FMT_HIP(c, hipMemcpyAsync(docNums[d].data(), c->mtNums.p + c->mtNumOffsHost[d], cnt[d] * sizeof(double),
+                                  hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  const auto t1 = clk::now();
+  // format on host threads
+  const fmt_kernels::SumDocOut* docs = c->sumHostDocs.p;
+  const fmt_kernels::SumV1Seg* segs = c->v1HostSegs.p;
+  const uint16_t* text = c->sumHostText.p;
+  SumDict D;
+  makeDict(D, keys, nKeys, values, nValues);
+  c->v1Blobs.assign(nd, std::string());
+  c->v1Ends.assign(nd, std::vector<uint64_t>());
+  c->v1Status.assign(nd, FMT_OK);
+  const uint32_t nt = threads ? threads : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  std::vector<std::thread> pool;
+  for (uint32_t t = 0; t < nt; t++)
+    pool.emplace_back([&, t] {
+      for (uint32_t d = t; d < nd; d += nt) {
+        const fmt_kernels::SumDocOut& o = docs[d];
+        if (static_cast<int32_t>(o.status) != FMT_OK) {
+          c->v1Status[d] = static_cast<int32_t>(o.status);
+          continue;
+        }
+        const std::vector<double>* nums = c->mtHasAdjust ? &docNums[d] : nullptr;
+        const uint32_t vBase = c->mtValueBaseHost.empty() ? 0u : c->mtValueBaseHost[d];
+        const uint64_t vEnd = c->mtValueBaseHost.empty() ? nValues : std::min<uint64_t>(nValues, c->mtValueBaseHost[d + 1] + 1ull);
+        const fmt_mt_propset* props = c->sumHostProps.p + propOff[d];
+        bool bad = docClientOffs[d + 1] < docClientOffs[d];
+        for (uint32_t i = 0; i < o.n_runs && !bad; i++)
+          bad = !propSetInTables(props, hdr[d].n_props, segs[o.run_off + i].props, nKeys, vBase, vEnd, nums);
+        if (bad) {
+          c->v1Status[d] = FMT_E_DATA;
+          continue;
+        }
+        std::string& out = c->v1Blobs[d];
+        out.reserve(o.n_units + 64ull * o.n_runs + 256);
+        c->v1Status[d] = v1Blobs(out, c->v1Ends[d], segs + o.run_off, o.n_runs, text + o.text_off, props,
+                                 c->v1HostRm.p + rmOff[d], static_cast<uint32_t>(rmOff[d + 1] - rmOff[d]),
+                                 clientNames + docClientOffs[d], docClientOffs[d + 1] - docClientOffs[d], hdr[d].min_seq,
+                                 hdr[d].cur_seq, chunk ? chunk : 10000u, D, nums, vBase);
+        if (c->v1Status[d] != FMT_OK) {
+          out.clear();
+          c->v1Ends[d].clear();
+        }
+      }
+    });
+  for (auto& th : pool) th.join();
+  const auto t2 = clk::now();
+  if (timing) {
+    timing->kernel_ms = kms;
+    timing->fetch_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    timing->format_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    uint64_t bytes = 0;
+    for (const auto& b : c->v1Blobs) bytes += b.size();
+    timing->bytes = bytes;
+    timing->threads = nt;
+  }
+  return FMT_OK;
+}
+
+int fmt_mt_summary_v1_blobs(fmt_ctx* c, uint32_t doc, const char** header, size_t* headerLen, uint32_t* nBodies) {
+  if (c == nullptr || doc >= c->v1Blobs.size()) return setErr(c, FMT_E_USAGE, "fmt_mt_summary_v1_blobs: no summary for doc");
+  if (c->v1Status[doc] != FMT_OK) return setErr(c, c->v1Status[doc], "document has no SnapshotV1 summary (its V1 status)");
+  if (header) *header = c->v1Blobs[doc].data();
+  if (headerLen) *headerLen = c->v1Ends[doc][0];
+  if (nBodies) *nBodies = static_cast<uint32_t>(c->v1Ends[doc].size() - 1);
+  return FMT_OK;
+}
+
+int fmt_mt_summary_v1_body(fmt_ctx* c, uint32_t doc, uint32_t k, const char** body, size_t* bodyLen) {
+  if (c == nullptr || doc >= c->v1Blobs.size()) return setErr(c, FMT_E_USAGE, "fmt_mt_summary_v1_body: no summary for doc");
+  if (c->v1Status[doc] != FMT_OK) return setErr(c, c->v1Status[doc], "document has no SnapshotV1 summary (its V1 status)");
+  const std::vector<uint64_t>& ends = c->v1Ends[doc];
+  if (k + 1ull >= ends.size()) return setErr(c, FMT_E_USAGE, "fmt_mt_summary_v1_body: no such body chunk");
+  if (body) *body = c->v1Blobs[doc].data() + ends[k];
+  if (bodyLen) *bodyLen = ends[k + 1] - ends[k];
   return FMT_OK;
 }
 
@@ -2202,6 +2509,38 @@ int fmt_internal_huge_profile(fmt_ctx* c, uint32_t doc, uint64_t* out) {
 
 // Test hook (not part of fmt.h): the summary formatters' JSON.stringify of a number (jsnum.h).
 int fmt_internal_js_number(double x, char* out, int cap) { return out == nullptr || cap < 0 ? 0 : fmt_json::jsNumber(x, out, cap); }
+
+// Test hook (not part of fmt_v1.h): fmt_mt_summarize_v1's host formatter (v1Blobs) over one document
+// given as host arrays, no device needed. segs: n_segs fmt_kernels::SumV1Seg records (kernels.h) and
+// their text back to back; rm: the remove-order entries (later stamps); numbers: the document's
+// computed annotate-adjust numbers or NULL; names[k]: JSON-quoted name of short client k. *out: the
+// header blob then the bodies, ends[0 .. *n_blobs) where each ends; both stay valid until the calling
+// thread's next call. Returns the document's V1 status (FMT_E_DATA: a prop set outside the tables).
+int fmt_internal_v1_format(const void* segs, uint32_t nSegs, const uint16_t* text, const fmt_mt_propset* props,
+                           uint32_t nProps, const fmt_mt_remove_order* rm, uint32_t nRm, const double* numbers,
+                           uint32_t nNumbers, const char* const* keys, uint32_t nKeys, const char* const* values,
+                           uint32_t nValues, const char* const* names, uint32_t nNames, int32_t minSeq, int32_t curSeq,
+                           uint32_t chunk, const char** out, const uint64_t** ends, uint32_t* nBlobs) {
+  static thread_local std::string blob;
+  static thread_local std::vector<uint64_t> blobEnds;
+  if (out == nullptr || ends == nullptr || nBlobs == nullptr || (nSegs && segs == nullptr)) return FMT_E_USAGE;
+  blob.clear();
+  blobEnds.clear();
+  const auto* S = static_cast<const fmt_kernels::SumV1Seg*>(segs);
+  SumDict D;
+  makeDict(D, keys, nKeys, values, nValues);
+  const std::vector<double> numVec(numbers, numbers + (numbers ? nNumbers : 0));
+  const std::vector<double>* nums = numbers ? &numVec : nullptr;
+  int rc = FMT_OK;
+  for (uint32_t i = 0; i < nSegs && rc == FMT_OK; i++)
+    if (!propSetInTables(props, nProps, S[i].props, nKeys, 0u, nValues, nums)) rc = FMT_E_DATA;
+  if (rc == FMT_OK) rc = v1Blobs(blob, blobEnds, S, nSegs, text, props, rm, nRm, names, nNames, minSeq, curSeq,
+                                 chunk ? chunk : 10000u, D, nums, 0u);
+  *out = blob.data();
+  *ends = blobEnds.data();
+  *nBlobs = rc == FMT_OK ? static_cast<uint32_t>(blobEnds.size()) : 0u;
+  return rc;
+}
 
 // Internal diagnostic (not part of fmt.h): per-phase cycle totals of a FMT_PROFILE=1 build.
 int fmt_internal_mt_profile(uint64_t* out, int n, int reset) {

@@ -1,0 +1,44 @@
+// sum_wave.h — the wave-level helpers the bulk summary kernels share (summary.hip, summary_v1.hip):
+// one wave per document, match classes of prop sets in LDS.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/fmt.h"
+
+namespace fmt_kernels {
+
+constexpr int kSumWaves = 4;
+constexpr int kSumMaxProps = 4096;  // prop sets per document (the huge tier's table)
+
+__device__ __forceinline__ void sumSync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint32_t sumUni(uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x))); }
+
+__device__ __forceinline__ uint32_t sumLane(uint32_t v, int lane) {
+  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), lane));
+}
+
+// Entry k of the prop set whose first record is p (fmt.h: wide sets take consecutive records).
+__device__ __forceinline__ uint32_t sumKv(const fmt_mt_propset* T, uint32_t p, uint32_t k) {
+  return T[p + k / FMT_MT_PROPS_MAX].kv[k % FMT_MT_PROPS_MAX];
+}
+
+// Sets p and q (first records, np records in all) hold the same (key, value) pairs, any order.
+__device__ __forceinline__ bool sumSameSet(const fmt_mt_propset* T, uint32_t p, uint32_t q, uint32_t np) {
+  const uint32_t n = T[p].n;
+  if (n != T[q].n || n == FMT_MT_PROPS_CONT || n > FMT_MT_PROPS_KEYS_MAX) return false;
+  if (p + (n ? (n - 1) / FMT_MT_PROPS_MAX : 0) >= np || q + (n ? (n - 1) / FMT_MT_PROPS_MAX : 0) >= np) return false;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t x = sumKv(T, p, i);
+    bool found = false;
+    for (uint32_t j = 0; j < n; j++) found = found || sumKv(T, q, j) == x;
+    if (!found) return false;
+  }
+  return true;
+}
+
+}  // namespace fmt_kernels

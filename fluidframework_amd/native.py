@@ -55,6 +55,12 @@ assert DOC_RESULT_DTYPE.itemsize == 48
 RM_ORDER_DTYPE = np.dtype([("leaf", "<u4"), ("client", "<i4"), ("seq", "<i4"), ("kind", "<u4")])
 LEAF_GONE = 0xFFFFFFFF
 
+# fmt_kernels::SumV1Seg (csrc/kernels.h): one SnapshotV1 summary segment as the bulk kernel writes it
+V1_SEG_DTYPE = np.dtype([("len", "<u4"), ("props", "<u2"), ("flags", "<u2"), ("leaf", "<u4"), ("ins_seq", "<i4"),
+                         ("ins_client", "<i4"), ("rm_client", "<i4"), ("rm_seq", "<i4"), ("rm_kind", "<u4")])
+assert V1_SEG_DTYPE.itemsize == 32
+V1_MARKER, V1_SOLO, V1_REMOVED = 1, 2, 4  # SumV1Seg.flags
+
 CATCHUP_DTYPE = np.dtype([("op", "<u4"), ("pos1", "<i4"), ("pos2", "<i4"), ("type", "<u4")])
 
 from .streams import (NO_MARKER, RELPOS_DTYPE, SNAPSHOT_DOC_DTYPE, SNAPSHOT_INFO_DTYPE, SNAPSHOT_SEG_DTYPE,  # noqa: E402
@@ -248,7 +254,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_fetch_rm_clients_hi2", [P, U32, P, U32]),
                            ("fmt_map_pending_run", [P, P, U64, P]),
                            ("fmt_mt_fetch_regen", [P, U32, P, U32, P, U32, ctypes.POINTER(U32), ctypes.POINTER(U32)]),
-                           ("fmt_map_pending_fetch", [P, P, P, P, U64, ctypes.POINTER(U64)])):
+                           ("fmt_map_pending_fetch", [P, P, P, P, U64, ctypes.POINTER(U64)]),
+                           ("fmt_mt_summarize_v1", [P, P, U32, P, U32, P, P, U32, U32, ctypes.POINTER(FmtSummaryTiming)]),
+                           ("fmt_mt_summary_v1_blobs", [P, U32, ctypes.POINTER(ctypes.c_char_p),
+                                                        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(U32)]),
+                           ("fmt_mt_summary_v1_body", [P, U32, U32, ctypes.POINTER(ctypes.c_char_p),
+                                                       ctypes.POINTER(ctypes.c_size_t)])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
                 getattr(L, name).argtypes = args
         _libs[path] = L
@@ -265,6 +276,43 @@ EXPORTED_SYMBOLS = [
     "fmt_mt_state_digest", "fmt_mt_fetch_legacy_props", "fmt_map_pending_run", "fmt_map_pending_fetch",
     "fmt_mt_fetch_regen", "fmt_mt_fetch_rm_clients_hi", "fmt_mt_fetch_rm_clients_hi2",
 ]
+
+
+# include/fmt_v1.h (bulk SnapshotV1 summaries)
+EXPORTED_SYMBOLS_V1 = ["fmt_mt_summarize_v1", "fmt_mt_summary_v1_blobs", "fmt_mt_summary_v1_body"]
+
+
+def _c_strings(strs):
+    enc = [x.encode("utf-8") for x in strs]
+    return (ctypes.c_char_p * max(len(enc), 1))(*enc), len(enc)
+
+
+def v1_format(segs, text, propsets, rm_order, keys, values, client_names, min_seq, cur_seq, chunk=10000, numbers=None):
+    """fmt_internal_v1_format: the bulk SnapshotV1 path's host formatter over one document's segment
+    records (V1_SEG_DTYPE, summary.v1_segment_records), no device needed. Returns (header, [bodies])."""
+    from .streams import js_quote
+
+    segs = np.ascontiguousarray(segs, dtype=V1_SEG_DTYPE)
+    text = np.ascontiguousarray(text, dtype="<u2")
+    propsets = np.ascontiguousarray(propsets, dtype=PROPSET_DTYPE)
+    rm_order = np.ascontiguousarray(rm_order, dtype=RM_ORDER_DTYPE)
+    nums = None if numbers is None or len(numbers) == 0 else np.ascontiguousarray(numbers, dtype=np.float64)
+    ka, nk = _c_strings(js_quote(k) for k in keys)
+    va, nv = _c_strings(values)
+    na, nn = _c_strings(js_quote(c) for c in client_names)
+    P, U32, I32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    f = lib().fmt_internal_v1_format
+    f.argtypes = [P, U32, P, P, U32, P, U32, P, U32, P, U32, P, U32, P, U32, I32, I32, U32, ctypes.POINTER(P),
+                  ctypes.POINTER(P), ctypes.POINTER(U32)]
+    out, ends, n = P(), P(), U32()
+    rc = f(_ptr(segs), len(segs), _ptr(text), _ptr(propsets), len(propsets), _ptr(rm_order), len(rm_order),
+           None if nums is None else _ptr(nums), 0 if nums is None else len(nums), ka, nk, va, nv, na, nn, min_seq, cur_seq,
+           chunk, ctypes.byref(out), ctypes.byref(ends), ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_v1_format")
+    e = [0] + list((ctypes.c_uint64 * n.value).from_address(ends.value))
+    blobs = [ctypes.string_at(out.value + e[k], e[k + 1] - e[k]).decode("utf-8") for k in range(n.value)]
+    return blobs[0], blobs[1:]
 
 
 def capacity():
@@ -399,6 +447,38 @@ class Engine:
         head = ctypes.string_at(h, hl.value).decode("utf-8")
         body = ctypes.string_at(b, bl.value).decode("utf-8") if bl.value else None
         return head, body
+
+    # ---- bulk SnapshotV1 summaries of the last merge-tree run (include/fmt_v1.h)
+    def mt_summarize_v1(self, keys, values, clients, chunk: int = 10000, threads: int = 0) -> dict:
+        """fmt_mt_summarize_v1: every document's SnapshotV1 blobs (device segmentation and first removers,
+        host JSON); clients[d][k]: the long id of document d's short client k (MergeTreeBatch.clients).
+        Returns the timing. Blobs: mt_summary_v1(doc)."""
+        from .streams import js_quote
+
+        ka, nk = _c_strings(js_quote(k) for k in keys)
+        va, nv = _c_strings(values)
+        offs = np.zeros(len(clients) + 1, dtype=np.uint64)
+        np.cumsum([len(c) for c in clients], out=offs[1:])
+        quoted = {}  # (each distinct name quoted once: batches repeat a few names over many documents)
+        flat = [quoted.setdefault(name, js_quote(name).encode("utf-8")) for c in clients for name in c]
+        ca = (ctypes.c_char_p * max(len(flat), 1))(*flat)
+        t = FmtSummaryTiming()
+        self._check(self.L.fmt_mt_summarize_v1(self.h, ka, nk, va, nv, ca, _ptr(offs), chunk, threads, ctypes.byref(t)))
+        return {"kernel_ms": t.kernel_ms, "fetch_ms": t.fetch_ms, "format_ms": t.format_ms, "bytes": int(t.bytes),
+                "threads": int(t.threads)}
+
+    def mt_summary_v1(self, doc: int):
+        """(header, [body_0, ...]) of document `doc` from the last mt_summarize_v1; EngineError with the
+        document's V1 status when it has none."""
+        h, hl, n = ctypes.c_char_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._check(self.L.fmt_mt_summary_v1_blobs(self.h, doc, ctypes.byref(h), ctypes.byref(hl), ctypes.byref(n)))
+        head = ctypes.string_at(h, hl.value).decode("utf-8")
+        bodies = []
+        for k in range(n.value):
+            b, bl = ctypes.c_char_p(), ctypes.c_size_t()
+            self._check(self.L.fmt_mt_summary_v1_body(self.h, doc, k, ctypes.byref(b), ctypes.byref(bl)))
+            bodies.append(ctypes.string_at(b, bl.value).decode("utf-8"))
+        return head, bodies
 
     # ---- merge-tree
     def mt_load(self, batch):

@@ -291,6 +291,62 @@ def v1_summary(header, leaves, chars, propsets, keys, values, client_names, remo
     return head, [body_of(c) + "}" for c in chunks[1:]]
 
 
+def v1_segment_records(header, leaves, chars, propsets, removers):
+    """The bulk SnapshotV1 kernel's output for one document, from fetched state: (segment records
+    (native.V1_SEG_DTYPE), their text back to back, the later remove stamps as remove-order entries
+    (native.RM_ORDER_DTYPE)). v1_segments' rule: a leaf removed at/below minSeq is skipped; an acked,
+    not-removed leaf at/below minSeq appends onto the open run while canAppend && matchProperties;
+    every other leaf closes the run and is a record of its own with its insert stamp and, when
+    removed, its first remove stamp (removers[leaf][0]; the rest go to the entries). Feeds
+    native.v1_format, the bulk path's host formatter, without a device."""
+    import numpy as np
+
+    from .native import RM_ORDER_DTYPE, V1_MARKER, V1_REMOVED, V1_SEG_DTYPE, V1_SOLO
+
+    min_seq = int(header["min_seq"])
+    segs, text, later = [], [], []
+    run = None  # [len, props id, props entries, marker, last unit]
+    for i in range(int(header["n_leaves"])):
+        L = leaves[i]
+        ins, rm = int(L["ins_seq"]), int(L["rm_seq"])
+        removed = rm != NOT_REMOVED
+        if removed and rm <= min_seq:
+            continue
+        o, n = int(L["char_off"]), int(L["len"])
+        text.append(chars[o : o + n])
+        marker = (int(L["pad"]) & MT_LEAF_MARKER) != 0
+        pid = int(L["props"])
+        props = None if pid == 0xFFFF else propset_entries(propsets, pid)
+        last = int(chars[o + n - 1]) if n else 0
+        if ins <= min_seq and not removed:
+            if (run is not None and not run[3] and not marker and run[4] != 10
+                    and (run[0] <= TEXT_GRANULARITY or n <= TEXT_GRANULARITY) and _props_match(run[2], props)):
+                run[0] += n
+                run[4] = last
+            else:
+                if run is not None:
+                    segs.append((run[0], run[1], V1_MARKER if run[3] else 0, 0, 0, 0, 0, 0, 0))
+                run = [n, pid, props, marker, last]
+            continue
+        if run is not None:
+            segs.append((run[0], run[1], V1_MARKER if run[3] else 0, 0, 0, 0, 0, 0, 0))
+            run = None
+        flags = V1_SOLO | (V1_MARKER if marker else 0)
+        first = (0, 0, 0)
+        if removed:
+            stamps = removers.get(i)
+            if not stamps:
+                raise ValueError(f"leaf {i}: remove order unknown (flag removes with FMT_MT_F_RMORDER)")
+            flags |= V1_REMOVED
+            first = stamps[0]
+            later.extend((i, c, s, k) for c, s, k in stamps[1:])
+        segs.append((n, pid, flags, i, ins, int(L["ins_client"]), first[0], first[1], first[2]))
+    if run is not None:
+        segs.append((run[0], run[1], V1_MARKER if run[3] else 0, 0, 0, 0, 0, 0, 0))
+    return (np.array(segs, dtype=V1_SEG_DTYPE), np.concatenate(text) if text else np.zeros(0, dtype="<u2"),
+            np.array(later, dtype=RM_ORDER_DTYPE))
+
+
 def _insert_seg_json(seg):
     """toJSONObject of the inserted segment's clone: a TextSegment's text, or {text, props} when it
     has properties (textSegment.ts:62-66; clone(props) drops null values, properties.ts:68-95); a

@@ -52,6 +52,7 @@ __device__ __forceinline__ void spSync() {
 }
 
 // Fibonacci hashing: the top log2(S) bits of key * 2^32/phi (one multiply; shift = 32 - log2 S).
+// (tests/map_edges.py sp_home mirrors this to choose colliding keys as inputs: change both together.)
 __device__ __forceinline__ uint32_t spHash(uint32_t k, uint32_t shift) { return (k * 0x9e3779b1u) >> shift; }
 
 template <int Ctrl, int RowMask>

@@ -543,6 +543,12 @@ static int mapValidate(fmt_ctx* c, const fmt_map_op* ops, uint64_t nOps, const u
   if (offs[0] != 0 || offs[nDocs] != nOps) return setErr(c, FMT_E_USAGE, "doc_op_offsets do not cover ops");
   for (uint32_t d = 0; d < nDocs; d++) {
     if (offs[d + 1] < offs[d]) return setErr(c, FMT_E_USAGE, "doc_op_offsets not monotone");
+    // seq 0 is the dense kernels' "no kill yet / no set yet" (map_lww.hip): a set at seq 0 would be dropped
+    if (offs[d + 1] > offs[d] && ops[offs[d]].seq == 0) {
+      char m[96];
+      std::snprintf(m, sizeof m, "doc %u: seq 0 (seqs are >= 1)", d);
+      return setErr(c, FMT_E_DATA, m);
+    }
     for (uint64_t i = offs[d] + 1; i < offs[d + 1]; i++) {
       if (ops[i].seq <= ops[i - 1].seq) {
         char m[128];

@@ -190,7 +190,9 @@ typedef struct fmt_mt_relpos {
 typedef struct fmt_map_op {
   uint32_t doc;
   uint32_t key;
-  uint32_t seq;        /* order key, strictly increasing within the document: the host packers store
+  uint32_t seq;        /* order key, >= 1 and strictly increasing within the document (seq 0 is refused
+                          with FMT_E_DATA by fmt_map_load / fmt_map_load_sparse: the dense kernels keep
+                          0 for "no delete, clear or set seen"): the host packers store
                           the message's 1-based ordinal in the document's stream, because messages of
                           one runtime bunch share their envelope's sequenceNumber
                           (shared-object-base/src/sharedObject.ts:620-630) */
@@ -471,7 +473,8 @@ int fmt_map_run(fmt_ctx* ctx);
 int fmt_map_fetch(fmt_ctx* ctx, fmt_map_slot* out);
 /* Zero-copy variant on caller-owned DEVICE buffers (e.g. torch tensors), launched on the ctx stream.
  * For key_bound > 2560 (the HBM-table path) d_out must be 8-byte aligned (FMT_E_USAGE otherwise).
- * Bad key ids (>= key_bound) are reported by fmt_map_check. */
+ * Bad key ids (>= key_bound) are reported by fmt_map_check. Precondition (no host validation here):
+ * every seq is >= 1 and strictly increasing within its document; a set at seq 0 is dropped. */
 int fmt_map_replay_device(fmt_ctx* ctx, const fmt_map_op* d_ops, const uint64_t* d_doc_op_offsets,
                           uint32_t n_docs, uint32_t key_bound, fmt_map_slot* d_out);
 /* Synchronizes the ctx stream; FMT_E_DATA when an op of the last map run referenced a key id

@@ -2548,6 +2548,41 @@ int fmt_internal_v1_format(const void* segs, uint32_t nSegs, const uint16_t* tex
   return rc;
 }
 
+// Test hook (not part of fmt.h): fmt_mt_summarize_legacy's host formatter (legacyBlobs) over one
+// document given as host arrays, no device needed. runs: n_runs fmt_kernels::SumRun records
+// (kernels.h) and their text back to back; numbers: the document's computed annotate-adjust numbers or
+// NULL. *out: the header blob then the body, ends[0 .. *n_blobs) where each ends (one blob: no body);
+// both stay valid until the calling thread's next call. Returns FMT_E_DATA for a prop set outside the
+// tables.
+int fmt_internal_legacy_format(const void* runs, uint32_t nRuns, const uint16_t* text, const fmt_mt_propset* props,
+                               uint32_t nProps, const double* numbers, uint32_t nNumbers, const char* const* keys,
+                               uint32_t nKeys, const char* const* values, uint32_t nValues, int32_t minSeq,
+                               uint32_t chunk, const char** out, const uint64_t** ends, uint32_t* nBlobs) {
+  static thread_local std::string blob;
+  static thread_local std::vector<uint64_t> blobEnds;
+  if (out == nullptr || ends == nullptr || nBlobs == nullptr || (nRuns && runs == nullptr)) return FMT_E_USAGE;
+  blob.clear();
+  blobEnds.clear();
+  const auto* R = static_cast<const fmt_kernels::SumRun*>(runs);
+  SumDict D;
+  makeDict(D, keys, nKeys, values, nValues);
+  const std::vector<double> numVec(numbers, numbers + (numbers ? nNumbers : 0));
+  const std::vector<double>* nums = numbers ? &numVec : nullptr;
+  int rc = FMT_OK;
+  for (uint32_t i = 0; i < nRuns && rc == FMT_OK; i++)
+    if (!propSetInTables(props, nProps, R[i].props, nKeys, 0u, nValues, nums)) rc = FMT_E_DATA;
+  if (rc == FMT_OK) {
+    uint32_t split = 0;
+    legacyBlobs(blob, &split, R, nRuns, text, props, minSeq, chunk ? chunk : 10000u, D, nums, 0u);
+    blobEnds.push_back(split);
+    if (blob.size() > split) blobEnds.push_back(blob.size());
+  }
+  *out = blob.data();
+  *ends = blobEnds.data();
+  *nBlobs = static_cast<uint32_t>(blobEnds.size());
+  return rc;
+}
+
 // Internal diagnostic (not part of fmt.h): per-phase cycle totals of a FMT_PROFILE=1 build.
 int fmt_internal_mt_profile(uint64_t* out, int n, int reset) {
   return fmt_kernels::mergeTreeProfile(out, n, reset != 0);

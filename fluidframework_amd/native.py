@@ -315,6 +315,36 @@ def v1_format(segs, text, propsets, rm_order, keys, values, client_names, min_se
     return blobs[0], blobs[1:]
 
 
+RUN_DTYPE = np.dtype([("len", "<u4"), ("props", "<u2"), ("flags", "<u2")])  # fmt_kernels::SumRun (csrc/kernels.h)
+assert RUN_DTYPE.itemsize == 8
+
+
+def legacy_format(runs, text, propsets, keys, values, min_seq, chunk=10000, numbers=None):
+    """fmt_internal_legacy_format: the bulk legacy path's host formatter over one document's runs
+    (RUN_DTYPE, summary.legacy_run_records), no device needed. Returns (header, body or None)."""
+    from .streams import js_quote
+
+    runs = np.ascontiguousarray(runs, dtype=RUN_DTYPE)
+    text = np.ascontiguousarray(text, dtype="<u2")
+    propsets = np.ascontiguousarray(propsets, dtype=PROPSET_DTYPE)
+    nums = None if numbers is None or len(numbers) == 0 else np.ascontiguousarray(numbers, dtype=np.float64)
+    ka, nk = _c_strings(js_quote(k) for k in keys)
+    va, nv = _c_strings(values)
+    P, U32, I32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    f = lib().fmt_internal_legacy_format
+    f.argtypes = [P, U32, P, P, U32, P, U32, P, U32, P, U32, I32, U32, ctypes.POINTER(P), ctypes.POINTER(P),
+                  ctypes.POINTER(U32)]
+    out, ends, n = P(), P(), U32()
+    rc = f(_ptr(runs), len(runs), _ptr(text), _ptr(propsets), len(propsets), None if nums is None else _ptr(nums),
+           0 if nums is None else len(nums), ka, nk, va, nv, min_seq, chunk, ctypes.byref(out), ctypes.byref(ends),
+           ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_legacy_format")
+    e = [0] + list((ctypes.c_uint64 * n.value).from_address(ends.value))
+    blobs = [ctypes.string_at(out.value + e[k], e[k + 1] - e[k]).decode("utf-8") for k in range(n.value)]
+    return blobs[0], (blobs[1] if len(blobs) > 1 else None)
+
+
 def capacity():
     a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
     lib().fmt_mt_capacity(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))

@@ -18,6 +18,7 @@ Semantics mirrored while packing:
 from __future__ import annotations
 
 import json
+import re
 from decimal import Decimal
 from dataclasses import dataclass, field
 
@@ -150,9 +151,16 @@ def js_key_order(keys):
 _JS_ESC = {'"': '\\"', "\\": "\\\\", "\b": "\\b", "\f": "\\f", "\n": "\\n", "\r": "\\r", "\t": "\\t"}
 
 
+_SURROGATE = re.compile("[\\ud800-\\udfff]")
+
+
 def js_quote(s: str) -> str:
     """JSON.stringify of a string (ECMAScript QuoteJSONString, well-formed JSON.stringify: lone
-    surrogates are escaped as \\udXXX, which json.dumps(ensure_ascii=False) would write raw)."""
+    surrogates are escaped as \\udXXX, which json.dumps(ensure_ascii=False) would write raw). A high
+    and a low surrogate that two concatenated Python strings left side by side are one code point
+    to JavaScript, whose strings are UTF-16: they are written as that character, not as two escapes."""
+    if _SURROGATE.search(s):
+        s = s.encode("utf-16-le", "surrogatepass").decode("utf-16-le", "surrogatepass")
     out = ['"']
     for ch in s:
         c = ord(ch)

@@ -141,6 +141,40 @@ def legacy_segments(header, leaves, chars, propsets, min_seq, legacy_props=None)
     return segs
 
 
+def legacy_run_records(header, leaves, chars, propsets, min_seq, legacy_props=None):
+    """The bulk legacy kernel's output for one document, from fetched state: (runs (native.RUN_DTYPE:
+    units, the head leaf's prop set id, marker flag), their text back to back). legacy_segments' rule
+    on the units themselves: a run ends in '\\n' when its last unit is 10. Feeds native.legacy_format,
+    the bulk path's host formatter, without a device."""
+    import numpy as np
+
+    from .native import RUN_DTYPE
+
+    runs, text = [], []
+    run = None  # [len, props id, props entries, marker, last unit]
+    for i, L in enumerate(leaves[: int(header["n_leaves"])]):
+        ins, rm = int(L["ins_seq"]), int(L["rm_seq"])
+        if not (ins <= min_seq) or rm <= min_seq:
+            continue
+        o, n = int(L["char_off"]), int(L["len"])
+        text.append(chars[o : o + n])
+        marker = (int(L["pad"]) & MT_LEAF_MARKER) != 0
+        pid = int(L["props"]) if legacy_props is None else int(legacy_props[i])
+        props = None if pid == 0xFFFF else propset_entries(propsets, pid)
+        last = int(chars[o + n - 1]) if n else 0
+        if (run is not None and not run[3] and not marker and run[4] != 10
+                and (run[0] <= TEXT_GRANULARITY or n <= TEXT_GRANULARITY) and _props_match(run[2], props)):
+            run[0] += n
+            run[4] = last
+        else:
+            if run is not None:
+                runs.append((run[0], run[1], 1 if run[3] else 0))
+            run = [n, pid, props, marker, last]
+    if run is not None:
+        runs.append((run[0], run[1], 1 if run[3] else 0))
+    return np.array(runs, dtype=RUN_DTYPE), np.concatenate(text) if text else np.zeros(0, dtype="<u2")
+
+
 def legacy_summary(header, leaves, chars, propsets, keys, values, chunk_size=SIZE_OF_FIRST_CHUNK, legacy_props=None):
     """(header_blob, body_blob or None) of the legacy SharedString summary at the doc's minSeq
     (legacy_props: the engine's getAtSeq prop set per leaf, batches with annotate-adjust)."""

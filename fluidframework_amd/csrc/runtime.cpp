@@ -19,6 +19,7 @@
 #include "huge_engine.h"
 #include "jsnum.h"
 #include "mt_engine.h"  // fmt_mt::AdjustTables
+#include "mt_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -170,15 +171,13 @@ struct fmt_ctx {
   uint64_t mtNSnapSegs = 0;
   uint32_t mtNRelpos = 0, mtMarkerKey = FMT_MT_NO_MARKER;
   bool mtHasSnap = false;
-  bool mtObliterate = false;                 // batch holds obliterates: launch the Doc<true> kernel
+  // what the loaded batch decided on the host (mt_plan.h): scan totals and flags, slab offsets, sorted
+  // numbers, the per-document facts of the huge tier. Replaced only by a batch that passes validation.
+  fmt_plan::MtPlan mtPlan;
   DevBuf<uint64_t> mtCuOffs;                 // per-doc catch-up slab offsets (n_docs + 1)
   DevBuf<fmt_mt_catchup_range> mtCatchup;    // catch-up range slabs
-  std::vector<uint64_t> mtCuOffsHost;
-  bool mtHasCatchup = false;
   DevBuf<uint64_t> mtRmOffs;                 // per-doc remove-order slab offsets (n_docs + 1)
   DevBuf<fmt_mt_remove_order> mtRmOrder;     // remove-order slabs (FMT_MT_F_RMORDER ops)
-  std::vector<uint64_t> mtRmOffsHost;
-  bool mtHasRmOrder = false;
   // huge documents (T3, huge_engine.h): one wave each, state in per-document HBM buffers
   struct HugeDocBufs {
     std::vector<void*> allocs;
@@ -189,25 +188,18 @@ struct fmt_ctx {
   };
   std::vector<HugeDocBufs> huge;             // per huge document
   std::vector<int32_t> mtHugeSlot;           // doc -> index in huge, or -1
-  // documents that outgrow the large tier replay again, from their start, in the huge tier when
-  // they hold nothing it does not (mtHugeOk: no SnapshotV1 body segments with merge info,
-  // FMT_MT_F_LOADSEG); their starts
-  std::vector<uint8_t> mtHugeOk;
-  std::vector<uint32_t> mtLoadSegs;          // per document: its FMT_MT_F_LOADSEG ops (V1 body segments)
-  std::vector<uint8_t> mtSegProps;           // per document: a loaded segment has properties
-  std::vector<uint64_t> mtDocChars;          // per document: start units + inserted units (its most text)
-  std::vector<fmt_mt_snapshot_seg> mtStartSeg;  // per document: its initial text as one segment (len 0: none)
+  // (documents that outgrow the large tier replay again in the huge tier, which holds every feature
+  // but local-client records; mtPlan keeps their starts)
   uint32_t mtHugeLoaded = 0;                 // huge documents routed at load (the rest were escalated)
   // documents refused at load (a feature the huge tier lacks, or no device memory for its state):
   // their headers are written at load and no tier runs them; the rest of the batch is unaffected
   std::vector<uint32_t> mtRefused;
   bool mtUseList = false;                    // the small tiers run mtSmallList (huge or refused docs)
   uint32_t mtGrown = 0;                      // documents the last run escalated into the huge tier
-  uint32_t mtNPropsOps = 0;
   std::vector<uint64_t> mtOffsHost;          // host copies of doc_op_offsets and the snapshot docs
   std::vector<fmt_mt_snapshot_doc> mtSnapHost;
   DevBuf<fmt_mt_snapshot_seg> mtStartSegDev;
-  DevBuf<fmt_huge::HugeState> hugeStates2;
+  DevBuf<fmt_huge::HugeState> hugeStates2;     // descriptors of the documents a run escalated (uploadHuge)
   DevBuf<fmt_huge::HugeInputs> hugeInputs2;
   DevBuf<fmt_kernels::HugeOut> hugeOuts2;
   // bulk legacy summaries (fmt_mt_summarize_legacy): device runs / text, host blobs
@@ -236,31 +228,24 @@ struct fmt_ctx {
   std::vector<uint32_t> mtValueBaseHost;         // empty: batch-global value ids
   DevBuf<uint64_t> mtNumOffs;
   DevBuf<fmt_mt::AdjustTables> mtAdjTab;      // the pointers above, for the kernels
-  std::vector<uint64_t> mtNumOffsHost;
   DevBuf<uint32_t> mtPm;                      // PropertiesManager records (4 words each) per document
   DevBuf<uint64_t> mtPmOffs;
-  std::vector<uint64_t> mtPmOffsHost;
   DevBuf<uint16_t> mtLegacy, mtBigLegacy;     // per leaf: the getAtSeq(minSeq) prop set (small / large slabs)
-  bool mtHasAdjust = false;
-  uint32_t mtNAdjusts = 0, mtNValues = 0, mtNNumSorted = 0;
   DevBuf<uint32_t> mtSmallList;              // the other documents (small tier), when huge ones exist
   // f4 (local-client records): every document replays in the compact tier's Loc variant first, the ones
   // it cannot hold in the small tier's, then the large tier's (round 6; mergetree_local.hip); its pending
   // groups, group records, PropertiesManager records, regenerated ops / text and normalization
   // scratch live in per-document slabs (mt_engine.h LocalTables)
-  bool mtLocal = false;
-  bool mtHiClients = false;  // some op or merge-info stamp names a short client id 64..253 (huge tier only)
   DevBuf<uint32_t> mtLocGroups, mtLocRecs, mtLocPm, mtLocScratch, mtLocRegenCount;
   DevBuf<uint64_t> mtLocOffs;                // 6 offset arrays of n + 1: groups, recs, pm, regen, text, scratch
   DevBuf<fmt_mt_op> mtLocRegen;
   DevBuf<uint16_t> mtLocRegenText;
   DevBuf<fmt_mt::LocalTables> mtLocTab;
-  std::vector<uint64_t> mtLocRegenOffsHost, mtLocRegenTextOffsHost;
   uint32_t mtNSmall = 0;
   DevBuf<fmt_huge::HugeState> hugeStates;
   DevBuf<fmt_huge::HugeInputs> hugeInputs;
   DevBuf<fmt_kernels::HugeOut> hugeOuts;
-  uint64_t mtNOps = 0, mtTextLen = 0, mtInsertChars = 0, mtInitChars = 0;
+  uint64_t mtNOps = 0, mtTextLen = 0;
   uint32_t mtDocs = 0, mtNProps = 0;
   bool mtHasInit = false, mtLoaded = false;
   bool mtRan = false;                         // fmt_mt_run completed for the loaded batch
@@ -290,22 +275,6 @@ int hipErr(fmt_ctx* c, hipError_t e, const char* what) {
     hipError_t e_ = (expr);                                \
     if (e_ != hipSuccess) return hipErr((ctx), e_, #expr); \
   } while (0)
-
-// Host threads for the runtime's own passes over a batch (validation, per-document sizing).
-unsigned hostWorkers() { return std::max(1u, std::min(16u, std::thread::hardware_concurrency())); }
-
-// fn(begin, end, worker) over hostWorkers() contiguous shares of [0, n) (one share below 2^16 items).
-template <class F>
-void parallelChunks(uint64_t n, F&& fn) {
-  const unsigned T = n < (1u << 16) ? 1u : hostWorkers();
-  if (T == 1) {
-    fn(0, n, 0u);
-    return;
-  }
-  std::vector<std::thread> pool;
-  for (unsigned t = 0; t < T; t++) pool.emplace_back([&, t] { fn(n * t / T, n * (t + 1) / T, t); });
-  for (auto& th : pool) th.join();
-}
 
 hipError_t stageInit(fmt_ctx* c) {
   Stager& S = c->stage;
@@ -882,7 +851,7 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   I.nPropsOps = nPropsOps;
   I.segs = segsDev;
   I.nSegs = static_cast<uint32_t>(N);
-  I.segProps = c->mtSegProps.empty() ? 0u : c->mtSegProps[d];
+  I.segProps = c->mtPlan.segProps[d];
   // SnapshotV1 merge info of a summary-loaded document's segments (header chunk)
   I.info = nullptr;
   I.stamps = c->mtHasSnapInfo ? c->mtSnapStamps.p : nullptr;
@@ -894,9 +863,9 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   I.catchup = nullptr;
   I.catchupCap = 0;
   S.cuIds = nullptr;
-  if (c->mtHasCatchup && c->mtCuOffsHost[d + 1] > c->mtCuOffsHost[d]) {
-    I.catchup = c->mtCatchup.p + c->mtCuOffsHost[d];
-    I.catchupCap = static_cast<uint32_t>(std::min<uint64_t>(c->mtCuOffsHost[d + 1] - c->mtCuOffsHost[d], 0xFFFFFFFFull));
+  if (c->mtPlan.hasCatchup() && c->mtPlan.cuOffs[d + 1] > c->mtPlan.cuOffs[d]) {
+    I.catchup = c->mtCatchup.p + c->mtPlan.cuOffs[d];
+    I.catchupCap = static_cast<uint32_t>(std::min<uint64_t>(c->mtPlan.cuOffs[d + 1] - c->mtPlan.cuOffs[d], 0xFFFFFFFFull));
     if ((e = alloc(static_cast<size_t>(S.idCap) * sizeof(uint32_t), &p)) != hipSuccess) return drop(e);
     S.cuIds = static_cast<uint32_t*>(p);
   }
@@ -906,10 +875,10 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   I.markerKey = c->mtMarkerKey;
   // annotate-adjust: the batch's tables (computed numbers, PropertiesManager records), the leaf id ->
   // output index map of the getAtSeq output
-  I.adj = c->mtHasAdjust ? c->mtAdjTab.p : nullptr;
+  I.adj = c->mtPlan.anyAdjust ? c->mtAdjTab.p : nullptr;
   I.doc = d;
   S.outIdx = nullptr;
-  if (c->mtHasAdjust) {
+  if (c->mtPlan.anyAdjust) {
     if ((e = alloc(static_cast<size_t>(S.idCap) * sizeof(uint32_t), &p)) != hipSuccess) return drop(e);
     S.outIdx = static_cast<uint32_t*>(p);
   }
@@ -924,9 +893,9 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   I.rmOrder = nullptr;
   I.rmOrderCap = 0;
   S.rmIds = nullptr;
-  if (c->mtHasRmOrder && c->mtRmOffsHost[d + 1] > c->mtRmOffsHost[d]) {
-    I.rmOrder = c->mtRmOrder.p + c->mtRmOffsHost[d];
-    I.rmOrderCap = static_cast<uint32_t>(std::min<uint64_t>(c->mtRmOffsHost[d + 1] - c->mtRmOffsHost[d], 0xFFFFFFFFull));
+  if (c->mtPlan.hasRmOrder() && c->mtPlan.rmOffs[d + 1] > c->mtPlan.rmOffs[d]) {
+    I.rmOrder = c->mtRmOrder.p + c->mtPlan.rmOffs[d];
+    I.rmOrderCap = static_cast<uint32_t>(std::min<uint64_t>(c->mtPlan.rmOffs[d + 1] - c->mtPlan.rmOffs[d], 0xFFFFFFFFull));
     if ((e = alloc(static_cast<size_t>(S.idCap) * sizeof(uint32_t), &p)) != hipSuccess) return drop(e);
     S.rmIds = static_cast<uint32_t*>(p);
   }
@@ -951,7 +920,7 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   O.props = static_cast<fmt_mt_propset*>(p);
   O.cls = S.pClass;
   O.legacy = nullptr;  // annotate-adjust batches: per leaf the getAtSeq(minSeq) prop set
-  if (c->mtHasAdjust) {
+  if (c->mtPlan.anyAdjust) {
     if ((e = alloc(O.capLeaves * sizeof(uint16_t), &p)) != hipSuccess) return drop(e);
     O.legacy = static_cast<uint16_t*>(p);
   }
@@ -960,7 +929,7 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   // live obliterates: at most one per op of the document is alive at once (HBM; batches with obliterates)
   S.obRec = S.obUsed = S.obSeq = S.obStart = nullptr;
   S.obCap = 0;
-  if (c->mtObliterate && nOps > 0) {
+  if (c->mtPlan.obliterates && nOps > 0) {
     if (nOps > 0x0FFFFFFFull) return drop(hipErrorOutOfMemory);
     S.obCap = static_cast<uint32_t>(std::max<uint64_t>(nOps, fmt_ckpt::kObSlots));  // (a checkpoint keeps its slot ids)
     if ((e = alloc(9ull * S.obCap * sizeof(uint32_t), &p)) != hipSuccess) return drop(e);
@@ -973,7 +942,7 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   // output (kHiOutWords 64-bit words per leaf: ids 64..127, 128..191, 192..253)
   S.hiMask = nullptr;
   O.leavesHi = nullptr;
-  if (c->mtHiClients) {
+  if (c->mtPlan.hiClients) {
     constexpr size_t kW = fmt_huge::kHiWords;
     if ((e = alloc(kW * S.idCap * sizeof(uint32_t), &p)) != hipSuccess) return drop(e);
     FMT_HIP(c, hipMemsetAsync(p, 0, kW * S.idCap * sizeof(uint32_t), c->stream));
@@ -984,155 +953,61 @@ static int setupHugeDoc(fmt_ctx* c, uint64_t textLen, uint32_t nPropsOps, uint32
   return FMT_OK;
 }
 
+// The descriptors of huge documents c->huge[first ..) as the arrays launchHugeDocs takes.
+static int uploadHuge(fmt_ctx* c, size_t first, DevBuf<fmt_huge::HugeState>& states, DevBuf<fmt_huge::HugeInputs>& inputs,
+                      DevBuf<fmt_kernels::HugeOut>& outs) {
+  const size_t nh = c->huge.size() - first;
+  if (nh == 0) return FMT_OK;
+  FMT_HIP(c, states.reserve(nh));
+  FMT_HIP(c, inputs.reserve(nh));
+  FMT_HIP(c, outs.reserve(nh));
+  std::vector<fmt_huge::HugeState> hs(nh);
+  std::vector<fmt_huge::HugeInputs> hi(nh);
+  std::vector<fmt_kernels::HugeOut> ho(nh);
+  for (size_t i = 0; i < nh; i++) {
+    hs[i] = c->huge[first + i].state;
+    hi[i] = c->huge[first + i].in;
+    ho[i] = c->huge[first + i].out;
+  }
+  FMT_HIP(c, hipMemcpyAsync(states.p, hs.data(), nh * sizeof(fmt_huge::HugeState), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipMemcpyAsync(inputs.p, hi.data(), nh * sizeof(fmt_huge::HugeInputs), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipMemcpyAsync(outs.p, ho.data(), nh * sizeof(fmt_kernels::HugeOut), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));  // (hs / hi / ho are about to go out of scope)
+  return FMT_OK;
+}
+
+// Plan (mt_plan.h: validation, slab sizing, routing; no device) then stage. A batch the plan refuses
+// leaves the context as it was: the batch loaded before stays loaded and runnable.
 int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
-  if (c == nullptr || b == nullptr || b->doc_op_offsets == nullptr || (b->n_ops && b->ops == nullptr))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_load: bad arguments");
-  const uint32_t n = b->n_docs;
-  if (b->doc_op_offsets[0] != 0 || b->doc_op_offsets[n] != b->n_ops)
-    return setErr(c, FMT_E_USAGE, "doc_op_offsets do not cover ops");
-  // one pass over the op records on host threads: counts, and the first invalid record
-  struct OpScan {
-    uint64_t insertChars = 0, catchupOps = 0, rmOrderOps = 0;
-    bool obliterates = false, local = false, hiClients = false;
-    uint64_t errAt = ~0ull;
-    int errCode = FMT_OK;
-    const char* err = nullptr;
-  };
-  std::vector<OpScan> scans(hostWorkers());
-  parallelChunks(b->n_ops, [&](uint64_t lo, uint64_t hi, unsigned t) {
-    OpScan& S = scans[t];
-    auto bad = [&](uint64_t i, int code, const char* what) {
-      S.errAt = i;
-      S.errCode = code;
-      S.err = what;
-    };
-    for (uint64_t i = lo; i < hi; i++) {
-      const fmt_mt_op& op = b->ops[i];
-      if (op.flags & FMT_MT_F_CATCHUP) S.catchupOps++;
-      if (op.flags & FMT_MT_F_RMORDER) S.rmOrderOps++;
-      if (op.flags & FMT_MT_F_LOCAL_ANY) S.local = true;
-      if (op.client > 63 && op.client != FMT_MT_CLIENT_NONCOLLAB) S.hiClients = true;
-      if (op.flags & FMT_MT_F_LOADSEG) {  // a SnapshotV1 body segment: its merge info row in range
-        if (op.type != FMT_MT_INSERT || b->snapshot_info == nullptr || op.pos1 < 0 ||
-            static_cast<uint64_t>(op.pos1) >= b->n_snapshot_segs ||
-            b->snapshot_info[op.pos1].rm_first + static_cast<uint64_t>(b->snapshot_info[op.pos1].rm_count) > b->n_snapshot_stamps) {
-          bad(i, FMT_E_DATA, "a loader segment (FMT_MT_F_LOADSEG) without a valid merge-info row");
-          return;
-        }
-      }
-      if (op.type == FMT_MT_INSERT) {
-        if (static_cast<uint64_t>(op.payload) + fmt_mt_op_len(&op) > b->text_len) {
-          bad(i, FMT_E_DATA, "insert payload outside the text arena");
-          return;
-        }
-        S.insertChars += fmt_mt_op_len(&op);
-      } else if (op.type == FMT_MT_ANNOTATE) {
-        if (op.payload >= b->n_props_ops) {
-          bad(i, FMT_E_DATA, "annotate props op id out of range");
-          return;
-        }
-      } else if (op.type == FMT_MT_OBLITERATE || op.type == FMT_MT_OBLITERATE_SIDED) {
-        S.obliterates = true;
-      } else if (op.type != FMT_MT_REMOVE) {
-        bad(i, FMT_E_UNSUPPORTED, "op type not supported by this engine build");
-        return;
-      }
-    }
-  });
-  uint64_t insertChars = 0, catchupOps = 0, rmOrderOps = 0;
-  bool obliterates = false, local = false, hiClients = false;
-  const OpScan* firstBad = nullptr;
-  for (const OpScan& S : scans) {
-    insertChars += S.insertChars;
-    catchupOps += S.catchupOps;
-    rmOrderOps += S.rmOrderOps;
-    obliterates = obliterates || S.obliterates;
-    local = local || S.local;
-    hiClients = hiClients || S.hiClients;
-    if (S.err != nullptr && (firstBad == nullptr || S.errAt < firstBad->errAt)) firstBad = &S;
-  }
-  if (firstBad != nullptr) return setErr(c, firstBad->errCode, firstBad->err);
-  // f4 batches run the Loc variants (annotate-adjust and remote ops with relative positions too since
-  // round 6): features they do not combine with are refused
-  if (local && (obliterates || catchupOps || rmOrderOps || b->snapshot_info != nullptr))
-    return setErr(c, FMT_E_UNSUPPORTED,
-                  "local-client records (FMT_MT_F_LOCAL_ANY) do not combine with obliterate, catch-up, remove order "
-                  "or SnapshotV1 merge info");
-  if (b->snapshots) {
-    for (uint32_t d = 0; d < n; d++) {
-      const fmt_mt_snapshot_doc& sd = b->snapshots[d];
-      if (!sd.loaded) continue;
-      if (b->snapshot_segs == nullptr || sd.first_seg + sd.n_header + sd.n_body > b->n_snapshot_segs)
-        return setErr(c, FMT_E_USAGE, "snapshot segments out of range");
-      for (uint64_t k = sd.first_seg; k < sd.first_seg + sd.n_header + sd.n_body; k++) {
-        const fmt_mt_snapshot_seg& sg = b->snapshot_segs[k];
-        const uint32_t len = sg.len & ~FMT_MT_SEG_MARKER;
-        if ((sg.len & FMT_MT_SEG_MARKER) != 0 && len != 1)
-          return setErr(c, FMT_E_DATA, "a marker segment has length 1");
-        if (static_cast<uint64_t>(sg.text) + len > b->text_len)
-          return setErr(c, FMT_E_DATA, "snapshot segment text outside the text arena");
-        if (sg.props != FMT_MT_NO_PROPS && sg.props >= b->n_props_ops)
-          return setErr(c, FMT_E_DATA, "snapshot segment props op id out of range");
-        insertChars += len;
-      }
-    }
-  }
-  uint64_t initChars = 0;
-  if (b->doc_init) {
-    for (uint32_t d = 0; d < n; d++) {
-      if (static_cast<uint64_t>(b->doc_init[2 * d]) + b->doc_init[2 * d + 1] > b->text_len)
-        return setErr(c, FMT_E_DATA, "initial text outside the text arena");
-      initChars += b->doc_init[2 * d + 1];
-    }
-  }
-  // Annotate-adjust entries (FMT_MT_VALUE_ADJUST + row index) in the props ops: validated here; per
-  // document they size its computed-number slab and decide whether its legacy summary is exact.
-  const uint32_t nKvAll = b->props_off ? b->props_off[b->n_props_ops] : 0;
-  std::vector<uint32_t> adjCount(b->n_props_ops, 0);  // adjust entries per props op
-  bool anyAdjust = false;
-  for (uint32_t op = 0; b->props_off && op < b->n_props_ops; op++) {
-    const uint32_t a = b->props_off[op], e = b->props_off[op + 1];
-    if (a > e || e > nKvAll) return setErr(c, FMT_E_USAGE, "props_off is not ascending");
-    for (uint32_t t = a; t < e; t++) {
-      const uint32_t v = b->props_kv[t] & 0xFFFFu;
-      if (v == FMT_MT_VALUE_ADJUST) {
-        if (t + 1 >= e || b->adjusts == nullptr || b->props_kv[t + 1] >= b->n_adjusts)
-          return setErr(c, FMT_E_DATA, "annotate-adjust entry without a valid adjust row");
-        adjCount[op]++;
-        anyAdjust = true;
-        t++;
-      }
-    }
-  }
-  if (b->doc_value_base != nullptr) {
-    for (uint32_t d = 0; d < n; d++)
-      if (b->doc_value_base[d + 1] < b->doc_value_base[d])
-        return setErr(c, FMT_E_USAGE, "doc_value_base is not ascending");
-    if (b->value_num != nullptr && b->doc_value_base[n] >= b->n_values)
-      return setErr(c, FMT_E_USAGE, "doc_value_base reaches past value_num");
-    c->mtValueBaseHost.assign(b->doc_value_base, b->doc_value_base + n + 1);
-  } else {
-    c->mtValueBaseHost.clear();
-  }
-  if (anyAdjust) {
-    if (b->value_num == nullptr && b->n_values > 0) return setErr(c, FMT_E_USAGE, "adjusts need value_num");
-    for (uint32_t t = 0; t < nKvAll; t++) {
-      const uint32_t v = b->props_kv[t] & 0xFFFFu;
-      if (v == FMT_MT_VALUE_ADJUST) {
-        t++;
-      } else if (v >= FMT_MT_VALUE_COMPUTED) {
-        return setErr(c, FMT_E_USAGE, "host value ids must stay below FMT_MT_VALUE_COMPUTED in a batch with adjusts");
-      }
-    }
-  }
+  if (c == nullptr) return FMT_E_USAGE;
   const fmt_kernels::MtCaps caps = fmt_kernels::mergeTreeCaps(false);
+  const char* why = nullptr;
+  // (the plan is built aside and moves into c->mtPlan only when the batch is valid)
+  const int planned = fmt_plan::planMergeTreeLoad(b, fmt_kernels::mergeTreeCaps(true), c->mtPlan, &why);
+  if (planned != FMT_OK) return setErr(c, planned, why);
+  const fmt_plan::MtPlan& P = c->mtPlan;
+  c->mtLoaded = false;  // (from here on the context holds this batch or, after a device error, none)
+  c->mtRan = false;
+  const uint32_t n = b->n_docs;
+  const uint32_t nKv = b->props_off ? b->props_off[b->n_props_ops] : 0;
+  // host arrays the asynchronous copies below read; the stream is drained before they go, on every way out
+  fmt_mt::AdjustTables adjTab{};
+  fmt_mt::LocalTables locTab{};
+  std::vector<fmt_mt_doc_result> refusedHdr;
+  std::vector<uint32_t> small;
+  struct Drain {
+    hipStream_t stream;
+    ~Drain() { (void)hipStreamSynchronize(stream); }
+  } drain{c->stream};
+  auto cp = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  };
   FMT_HIP(c, hipSetDevice(c->device));
   FMT_HIP(c, c->mtOps.reserve(b->n_ops));
   FMT_HIP(c, c->mtOffs.reserve(n + 1ull));
   FMT_HIP(c, c->mtText.reserve(b->text_len));
   FMT_HIP(c, c->mtInit.reserve(2ull * n));
   FMT_HIP(c, c->mtPropsOff.reserve(b->n_props_ops + 1ull));
-  const uint32_t nKv = b->props_off ? b->props_off[b->n_props_ops] : 0;
   FMT_HIP(c, c->mtPropsKv.reserve(nKv));
   FMT_HIP(c, c->mtHdr.reserve(n));
   FMT_HIP(c, c->mtLeaves.reserve(static_cast<size_t>(n) * caps.leaves));
@@ -1144,120 +1019,56 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   FMT_HIP(c, c->mtEsc4.reserve(n + 1ull));
   FMT_HIP(c, c->mtSched.reserve(4));
   c->mtBigSlot.assign(n, -1);
-  // Catch-up slabs: kCatchupPerOp ranges per flagged op plus kCatchupPerDoc per document that has
-  // any; a document that needs more reports FMT_E_CAPACITY.
-  c->mtHasCatchup = catchupOps > 0;
-  if (c->mtHasCatchup) {
-    constexpr uint64_t kCatchupPerOp = 16, kCatchupPerDoc = 16;
-    c->mtCuOffsHost.assign(n + 1ull, 0);
-    for (uint32_t d = 0; d < n; d++) {
-      uint64_t f = 0;
-      for (uint64_t i = b->doc_op_offsets[d]; i < b->doc_op_offsets[d + 1]; i++)
-        f += (b->ops[i].flags & FMT_MT_F_CATCHUP) ? 1 : 0;
-      c->mtCuOffsHost[d + 1] = c->mtCuOffsHost[d] + (f ? f * kCatchupPerOp + kCatchupPerDoc : 0);
-    }
+  // catch-up and remove-order slabs (sizes: mt_plan.h catchupSlab / rmOrderSlab)
+  if (P.hasCatchup()) {
     FMT_HIP(c, c->mtCuOffs.reserve(n + 1ull));
-    FMT_HIP(c, c->mtCatchup.reserve(c->mtCuOffsHost[n]));
+    FMT_HIP(c, c->mtCatchup.reserve(P.cuOffs[n]));
+    FMT_HIP(c, cp(c->mtCuOffs.p, P.cuOffs.data(), (n + 1ull) * sizeof(uint64_t)));
   }
-  // Remove-order slabs: kRmPerOp entries per flagged remove plus kRmPerDoc per document that has
-  // any (split copies included); a document that needs more reports FMT_E_CAPACITY.
-  c->mtHasRmOrder = rmOrderOps > 0;
-  if (c->mtHasRmOrder) {
-    constexpr uint64_t kRmPerOp = 64, kRmPerDoc = 256;
-    c->mtRmOffsHost.assign(n + 1ull, 0);
-    for (uint32_t d = 0; d < n; d++) {
-      uint64_t f = 0;
-      for (uint64_t i = b->doc_op_offsets[d]; i < b->doc_op_offsets[d + 1]; i++)
-        f += (b->ops[i].flags & FMT_MT_F_RMORDER) ? 1 : 0;
-      c->mtRmOffsHost[d + 1] = c->mtRmOffsHost[d] + (f ? f * kRmPerOp + kRmPerDoc : 0);
-    }
+  if (P.hasRmOrder()) {
     FMT_HIP(c, c->mtRmOffs.reserve(n + 1ull));
-    FMT_HIP(c, c->mtRmOrder.reserve(c->mtRmOffsHost[n]));
+    FMT_HIP(c, c->mtRmOrder.reserve(P.rmOffs[n]));
+    FMT_HIP(c, cp(c->mtRmOffs.p, P.rmOffs.data(), (n + 1ull) * sizeof(uint64_t)));
   }
-  auto cp = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  };
-  // Computed-number slabs: 64 per adjust entry of the document's annotates + 64 (at most 0x7fff, the
-  // computed id range: one adjust over a range can compute a new number per leaf it hits); a document
-  // that computes more distinct numbers reports FMT_E_CAPACITY. PropertiesManager record slabs
-  // (mt_engine.h Doc::pm*): 32 per change of the document's annotates + 256 records.
-  c->mtHasAdjust = anyAdjust;
-  if (anyAdjust) {
-    c->mtNumOffsHost.assign(n + 1ull, 0);
-    c->mtPmOffsHost.assign(n + 1ull, 0);
-    for (uint32_t d = 0; d < n; d++) {
-      uint64_t f = 0, g = 0;
-      for (uint64_t i = b->doc_op_offsets[d]; i < b->doc_op_offsets[d + 1]; i++) {
-        const fmt_mt_op& op = b->ops[i];
-        if (op.type != FMT_MT_ANNOTATE) continue;
-        f += adjCount[op.payload];
-        g += b->props_off[op.payload + 1] - b->props_off[op.payload];
-      }
-      c->mtNumOffsHost[d + 1] = c->mtNumOffsHost[d] + (f ? std::min<uint64_t>(64 * f + 64, 0x7FFF) : 0);
-      c->mtPmOffsHost[d + 1] = c->mtPmOffsHost[d] + (g ? std::min<uint64_t>(32 * g + 256, 1u << 20) : 0);
-    }
-    // the host's numbers, ascending, each with the first value id that holds it: one list for the
-    // batch, or per document with its local ids (doc_value_base)
-    std::vector<double> sv;
-    std::vector<uint32_t> si, so;
-    auto sortNumbers = [&](uint32_t lo, uint32_t hi, uint32_t base) {
-      std::vector<std::pair<double, uint32_t>> nums;
-      for (uint32_t i = lo; b->value_num && i < hi; i++)
-        if (b->value_num[base + i] == b->value_num[base + i])
-          nums.emplace_back(b->value_num[base + i] == 0.0 ? 0.0 : b->value_num[base + i], i);
-      std::stable_sort(nums.begin(), nums.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-      const size_t first = sv.size();
-      for (const auto& [x, i] : nums) {
-        if (sv.size() > first && sv.back() == x) continue;  // (one text per number: the first id)
-        sv.push_back(x);
-        si.push_back(i);
-      }
-    };
-    if (b->doc_value_base != nullptr) {
-      so.assign(1, 0);
-      for (uint32_t d = 0; d < n; d++) {
-        sortNumbers(1, b->doc_value_base[d + 1] - b->doc_value_base[d] + 1, b->doc_value_base[d]);
-        so.push_back(static_cast<uint32_t>(sv.size()));
-      }
-    } else {
-      sortNumbers(0, b->n_values, 0);
-    }
-    c->mtNAdjusts = b->n_adjusts;
-    c->mtNValues = b->value_num ? b->n_values : 0u;
-    c->mtNNumSorted = static_cast<uint32_t>(sv.size());
+  // annotate-adjust: the rows, the host numbers (plain and sorted for number → id lookups), and the
+  // per-document computed-number and PropertiesManager slabs (mt_plan.h numberSlab / pmSlab)
+  if (b->doc_value_base != nullptr) c->mtValueBaseHost.assign(b->doc_value_base, b->doc_value_base + n + 1);
+  else c->mtValueBaseHost.clear();
+  if (P.anyAdjust) {
+    const uint32_t nValues = b->value_num ? b->n_values : 0u;
     FMT_HIP(c, c->mtAdjusts.reserve(b->n_adjusts));
-    FMT_HIP(c, c->mtValueNum.reserve(c->mtNValues));
-    FMT_HIP(c, c->mtNumSorted.reserve(sv.size()));
-    FMT_HIP(c, c->mtNumSortedId.reserve(si.size()));
+    FMT_HIP(c, c->mtValueNum.reserve(nValues));
+    FMT_HIP(c, c->mtNumSorted.reserve(P.numSorted.size()));
+    FMT_HIP(c, c->mtNumSortedId.reserve(P.numSortedId.size()));
     FMT_HIP(c, c->mtNumOffs.reserve(n + 1ull));
-    FMT_HIP(c, c->mtNums.reserve(c->mtNumOffsHost[n]));
+    FMT_HIP(c, c->mtNums.reserve(P.numOffs[n]));
     FMT_HIP(c, c->mtNumCount.reserve(n));
     FMT_HIP(c, c->mtPmOffs.reserve(n + 1ull));
-    FMT_HIP(c, c->mtPm.reserve(4 * c->mtPmOffsHost[n]));
+    FMT_HIP(c, c->mtPm.reserve(4 * P.pmOffs[n]));
     FMT_HIP(c, c->mtLegacy.reserve(static_cast<size_t>(n) * caps.leaves));
-    FMT_HIP(c, cp(c->mtPmOffs.p, c->mtPmOffsHost.data(), (n + 1ull) * sizeof(uint64_t)));
+    FMT_HIP(c, cp(c->mtPmOffs.p, P.pmOffs.data(), (n + 1ull) * sizeof(uint64_t)));
     FMT_HIP(c, cp(c->mtAdjusts.p, b->adjusts, b->n_adjusts * sizeof(fmt_mt_adjust)));
-    FMT_HIP(c, cp(c->mtValueNum.p, b->value_num, c->mtNValues * sizeof(double)));
-    FMT_HIP(c, cp(c->mtNumSorted.p, sv.data(), sv.size() * sizeof(double)));
-    FMT_HIP(c, cp(c->mtNumSortedId.p, si.data(), si.size() * sizeof(uint32_t)));
+    FMT_HIP(c, cp(c->mtValueNum.p, b->value_num, nValues * sizeof(double)));
+    FMT_HIP(c, cp(c->mtNumSorted.p, P.numSorted.data(), P.numSorted.size() * sizeof(double)));
+    FMT_HIP(c, cp(c->mtNumSortedId.p, P.numSortedId.data(), P.numSortedId.size() * sizeof(uint32_t)));
     if (b->doc_value_base != nullptr) {
       FMT_HIP(c, c->mtValueBase.reserve(n + 1ull));
       FMT_HIP(c, c->mtNumSortedOffs.reserve(n + 1ull));
       FMT_HIP(c, cp(c->mtValueBase.p, b->doc_value_base, (n + 1ull) * sizeof(uint32_t)));
-      FMT_HIP(c, cp(c->mtNumSortedOffs.p, so.data(), (n + 1ull) * sizeof(uint32_t)));
+      FMT_HIP(c, cp(c->mtNumSortedOffs.p, P.numSortedOffs.data(), (n + 1ull) * sizeof(uint32_t)));
     }
-    FMT_HIP(c, cp(c->mtNumOffs.p, c->mtNumOffsHost.data(), (n + 1ull) * sizeof(uint64_t)));
+    FMT_HIP(c, cp(c->mtNumOffs.p, P.numOffs.data(), (n + 1ull) * sizeof(uint64_t)));
     FMT_HIP(c, hipMemsetAsync(c->mtNumCount.p, 0, n * sizeof(uint32_t), c->stream));
-    fmt_mt::AdjustTables T{};
+    fmt_mt::AdjustTables& T = adjTab;
     T.adjusts = c->mtAdjusts.p;
     T.nAdjusts = b->n_adjusts;
-    T.nValues = c->mtNValues;
+    T.nValues = nValues;
     T.valueNum = c->mtValueNum.p;
     T.numSorted = c->mtNumSorted.p;
     T.numSortedId = c->mtNumSortedId.p;
     T.valueBase = b->doc_value_base != nullptr ? c->mtValueBase.p : nullptr;
     T.numSortedOffs = b->doc_value_base != nullptr ? c->mtNumSortedOffs.p : nullptr;
-    T.nNumSorted = c->mtNNumSorted;
+    T.nNumSorted = static_cast<uint32_t>(P.numSorted.size());
     T.nums = c->mtNums.p;
     T.numOffsets = c->mtNumOffs.p;
     T.numCount = c->mtNumCount.p;
@@ -1265,60 +1076,27 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     T.pmOffsets = c->mtPmOffs.p;
     FMT_HIP(c, c->mtAdjTab.reserve(1));
     FMT_HIP(c, cp(c->mtAdjTab.p, &T, sizeof T));
-    FMT_HIP(c, hipStreamSynchronize(c->stream));  // (sv / si / T are about to go out of scope)
   }
-  c->mtLocal = local;
-  c->mtRan = false;
-  c->mtHiClients = hiClients;
-  if (local) {
-    // Per-document slabs, sized from the document's local records (a document that needs more reports
-    // FMT_E_CAPACITY): 4 + 2 pending groups per submission (a reconnect replaces a group by one per
-    // segment), 32 group records per submission (hits and split copies; deleted ones compact away),
-    // 64 PropertiesManager records per key of a local annotate (annotate-adjust batches: + 32 per key
-    // of any annotate, whose remote changes stay listed until minSeq passes them), regenerated ops /
-    // text per reconnect, and normalization scratch for a document that reconnects.
-    const fmt_kernels::MtCaps big = fmt_kernels::mergeTreeCaps(true);
-    std::vector<uint64_t> offs(6 * (n + 1ull), 0);
-    for (uint32_t d = 0; d < n; d++) {
-      uint64_t sub = 0, keys = 0, regens = 0, text = 0;
-      for (uint64_t i = b->doc_op_offsets[d]; i < b->doc_op_offsets[d + 1]; i++) {
-        const fmt_mt_op& op = b->ops[i];
-        if (op.flags & FMT_MT_F_REGEN) regens++;
-        if (anyAdjust && op.type == FMT_MT_ANNOTATE && !(op.flags & (FMT_MT_F_LOCAL | FMT_MT_F_ROLLBACK)))
-          keys += (b->props_off[op.payload + 1] - b->props_off[op.payload] + 1) / 2;
-        if (!(op.flags & FMT_MT_F_LOCAL)) continue;
-        sub++;
-        if (op.type == FMT_MT_INSERT) text += fmt_mt_op_len(&op);
-        if (op.type == FMT_MT_ANNOTATE) keys += b->props_off[op.payload + 1] - b->props_off[op.payload];
-      }
-      const uint64_t cap[6] = {sub ? std::min<uint64_t>(6 * sub + 64 + (regens ? big.leaves : 0), 1u << 22) : 0,
-                               sub ? std::min<uint64_t>(32 * sub + 1024, 1u << 24) : 0,
-                               keys ? std::min<uint64_t>(64 * keys + 512, 1u << 22) : 0,
-                               regens ? std::min<uint64_t>(regens * std::min<uint64_t>(8 * sub + 64, big.leaves), 1u << 22) : 0,
-                               regens ? std::min<uint64_t>(regens * std::min<uint64_t>(text, big.chars) + 64, 1u << 26) : 0,
-                               regens ? 15ull * big.leaves + big.chars / 2 + 64 : 0};
-      for (int k = 0; k < 6; k++) offs[k * (n + 1ull) + d + 1] = offs[k * (n + 1ull) + d] + cap[k];
-    }
-    auto total = [&](int k) { return offs[k * (n + 1ull) + n]; };
-    FMT_HIP(c, c->mtLocOffs.reserve(6 * (n + 1ull)));
-    FMT_HIP(c, c->mtLocGroups.reserve(8 * total(0)));
-    FMT_HIP(c, c->mtLocRecs.reserve(2 * total(1)));
-    FMT_HIP(c, c->mtLocPm.reserve(4 * total(2)));
-    FMT_HIP(c, c->mtLocRegen.reserve(total(3)));
-    FMT_HIP(c, c->mtLocRegenText.reserve(total(4)));
-    FMT_HIP(c, c->mtLocScratch.reserve(total(5)));
+  // f4: the per-document slabs of the local records (mt_plan.h localSlabs)
+  if (P.local) {
+    const uint64_t n1 = n + 1ull;
+    FMT_HIP(c, c->mtLocOffs.reserve(P.locOffs.size()));
+    FMT_HIP(c, c->mtLocGroups.reserve(8 * P.locSlabOffs(fmt_plan::kLocGroups)[n]));
+    FMT_HIP(c, c->mtLocRecs.reserve(2 * P.locSlabOffs(fmt_plan::kLocRecs)[n]));
+    FMT_HIP(c, c->mtLocPm.reserve(4 * P.locSlabOffs(fmt_plan::kLocPm)[n]));
+    FMT_HIP(c, c->mtLocRegen.reserve(P.locSlabOffs(fmt_plan::kLocRegen)[n]));
+    FMT_HIP(c, c->mtLocRegenText.reserve(P.locSlabOffs(fmt_plan::kLocRegenText)[n]));
+    FMT_HIP(c, c->mtLocScratch.reserve(P.locSlabOffs(fmt_plan::kLocScratch)[n]));
     FMT_HIP(c, c->mtLocRegenCount.reserve(2ull * n));
     FMT_HIP(c, c->mtLocTab.reserve(1));
-    FMT_HIP(c, cp(c->mtLocOffs.p, offs.data(), offs.size() * sizeof(uint64_t)));
+    FMT_HIP(c, cp(c->mtLocOffs.p, P.locOffs.data(), P.locOffs.size() * sizeof(uint64_t)));
     FMT_HIP(c, hipMemsetAsync(c->mtLocRegenCount.p, 0, 2ull * n * sizeof(uint32_t), c->stream));
     const uint64_t* O = c->mtLocOffs.p;
-    fmt_mt::LocalTables T{c->mtLocGroups.p, O, c->mtLocRecs.p, O + (n + 1ull), c->mtLocPm.p, O + 2 * (n + 1ull),
-                          c->mtLocRegen.p, O + 3 * (n + 1ull), c->mtLocRegenText.p, O + 4 * (n + 1ull),
-                          c->mtLocRegenCount.p, c->mtLocScratch.p, O + 5 * (n + 1ull)};
-    FMT_HIP(c, cp(c->mtLocTab.p, &T, sizeof T));
-    c->mtLocRegenOffsHost.assign(offs.begin() + 3 * (n + 1ull), offs.begin() + 4 * (n + 1ull));
-    c->mtLocRegenTextOffsHost.assign(offs.begin() + 4 * (n + 1ull), offs.begin() + 5 * (n + 1ull));
-    FMT_HIP(c, hipStreamSynchronize(c->stream));  // (offs / T are about to go out of scope)
+    locTab = fmt_mt::LocalTables{c->mtLocGroups.p, O + fmt_plan::kLocGroups * n1, c->mtLocRecs.p, O + fmt_plan::kLocRecs * n1,
+                                 c->mtLocPm.p, O + fmt_plan::kLocPm * n1, c->mtLocRegen.p, O + fmt_plan::kLocRegen * n1,
+                                 c->mtLocRegenText.p, O + fmt_plan::kLocRegenText * n1, c->mtLocRegenCount.p,
+                                 c->mtLocScratch.p, O + fmt_plan::kLocScratch * n1};
+    FMT_HIP(c, cp(c->mtLocTab.p, &locTab, sizeof locTab));
   }
   FMT_HIP(c, stagedCopy(c, c->mtOps.p, b->ops, b->n_ops * sizeof(fmt_mt_op), true));
   FMT_HIP(c, cp(c->mtOffs.p, b->doc_op_offsets, (n + 1ull) * sizeof(uint64_t)));
@@ -1338,8 +1116,6 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     FMT_HIP(c, c->mtSnapStamps.reserve(b->n_snapshot_stamps));
     FMT_HIP(c, cp(c->mtSnapInfo.p, b->snapshot_info, b->n_snapshot_segs * sizeof(fmt_mt_snapshot_info)));
     FMT_HIP(c, cp(c->mtSnapStamps.p, b->snapshot_stamps, b->n_snapshot_stamps * sizeof(fmt_mt_stamp)));
-    for (uint64_t k = 0; k < b->n_snapshot_stamps && !c->mtHiClients; k++) c->mtHiClients = b->snapshot_stamps[k].client > 63;
-    for (uint64_t k = 0; k < b->n_snapshot_segs && !c->mtHiClients; k++) c->mtHiClients = b->snapshot_info[k].ins_client > 63;
   }
   c->mtNRelpos = b->relpos ? b->n_relpos : 0u;
   c->mtMarkerKey = b->marker_id_key;
@@ -1347,8 +1123,6 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     FMT_HIP(c, c->mtRelpos.reserve(c->mtNRelpos));
     FMT_HIP(c, cp(c->mtRelpos.p, b->relpos, c->mtNRelpos * sizeof(fmt_mt_relpos)));
   }
-  if (c->mtHasCatchup) FMT_HIP(c, cp(c->mtCuOffs.p, c->mtCuOffsHost.data(), (n + 1ull) * sizeof(uint64_t)));
-  if (c->mtHasRmOrder) FMT_HIP(c, cp(c->mtRmOffs.p, c->mtRmOffsHost.data(), (n + 1ull) * sizeof(uint64_t)));
   if (b->props_off) {
     FMT_HIP(c, cp(c->mtPropsOff.p, b->props_off, (b->n_props_ops + 1ull) * sizeof(uint32_t)));
     FMT_HIP(c, cp(c->mtPropsKv.p, b->props_kv, nKv * sizeof(uint32_t)));
@@ -1359,18 +1133,16 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   c->mtNOps = b->n_ops;
   c->mtDocs = n;
   c->mtTextLen = b->text_len;
-  c->mtNPropsOps = b->n_props_ops;
+  c->mtNProps = b->n_props_ops;
   c->mtOffsHost.assign(b->doc_op_offsets, b->doc_op_offsets + n + 1);
   if (b->snapshots) c->mtSnapHost.assign(b->snapshots, b->snapshots + n);
   else c->mtSnapHost.clear();
-  c->mtNProps = b->n_props_ops;
   c->mtHasInit = b->doc_init != nullptr;
-  c->mtObliterate = obliterates;
   // A batch without remove-order recording starts in the micro tier (with obliterates: the compact
   // tier); a document about to outgrow a tier stops at a checkpoint (one slot of ≈17 KiB per document)
   // that the next tier resumes from.
   c->mtCkptOk = false;
-  if (!c->mtHasRmOrder) {
+  if (!P.hasRmOrder()) {
     // (a batch too large for the checkpoints still replays: overflowing documents then restart in
     // the next tier from their first op, as batches with obliterates do)
     c->mtCkptOk = c->mtCkpt.reserve(static_cast<size_t>(n) * (fmt_kernels::mergeTreeCheckpointBytes() / sizeof(uint32_t))) ==
@@ -1379,123 +1151,49 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   }
   // plain batches with checkpoints: the lists of the rounds in which documents step down a tier
   c->mtDescWords = 0;
-  if (c->mtCkptOk && !obliterates && !c->mtHasAdjust && !c->mtLocal) {
+  if (c->mtCkptOk && !P.obliterates && !P.anyAdjust && !P.local) {
     const size_t words = fmt_kernels::mergeTreeDescendWords(n);
     if (c->mtDesc.reserve(words) == hipSuccess) c->mtDescWords = words;
     else (void)hipGetLastError();
   }
-  c->mtInsertChars = insertChars;
-  c->mtInitChars = initChars;
   // Huge documents: a summary-loaded document with more segments or text than the large tier holds
-  // is replayed by the huge-document engine (huge_engine.h: one wave, state in HBM). It loads from
-  // one header chunk; catch-up / remove-order recording stays with the other tiers.
+  // is replayed by the huge-document engine (huge_engine.h: one wave, state in HBM). One the plan
+  // refused (local-client records), or whose state does not fit in device memory, fails alone at load
+  // (its header says why) and the rest of the batch replays.
   for (auto& h : c->huge)
     for (void* p : h.allocs) (void)hipFree(p);
   c->huge.clear();
   c->mtHugeSlot.assign(n, -1);
-  c->mtHugeOk.assign(n, 1);
-  c->mtLoadSegs.assign(n, 0);
-  c->mtSegProps.assign(n, 0);
-  c->mtDocChars.assign(n, 0);
-  c->mtStartSeg.assign(n, fmt_mt_snapshot_seg{0, 0, FMT_MT_NO_PROPS});
-  parallelChunks(n, [&](uint64_t d0, uint64_t d1, unsigned) {
-  for (uint64_t d = d0; d < d1; d++) {
-    uint8_t ok = 1;  // (the huge tier replays every feature a document of the other tiers may hold)
-    uint64_t chars = 0;
-    uint32_t loadSegs = 0;
-    for (uint64_t i = b->doc_op_offsets[d]; i < b->doc_op_offsets[d + 1]; i++) {
-      const fmt_mt_op& op = b->ops[i];
-      if (op.type == FMT_MT_INSERT) chars += fmt_mt_op_len(&op);
-      if (op.flags & FMT_MT_F_LOADSEG) loadSegs++;
-    }
-    c->mtLoadSegs[d] = loadSegs;
-    if (b->snapshots && b->snapshots[d].loaded) {
-      const fmt_mt_snapshot_doc& sd = b->snapshots[d];
-      for (uint64_t k = sd.first_seg; k < sd.first_seg + sd.n_header + sd.n_body; k++)
-        if (b->snapshot_segs[k].props != FMT_MT_NO_PROPS) {
-          c->mtSegProps[d] = 1;
-          break;
-        }
-      for (uint64_t k = sd.first_seg; k < sd.first_seg + sd.n_header + sd.n_body; k++)
-        chars += b->snapshot_segs[k].len & ~FMT_MT_SEG_MARKER;
-    } else if (b->doc_init && b->doc_init[2 * d + 1] > 0) {
-      c->mtStartSeg[d] = fmt_mt_snapshot_seg{b->doc_init[2 * d], b->doc_init[2 * d + 1], FMT_MT_NO_PROPS};
-      chars += b->doc_init[2 * d + 1];
-    }
-    c->mtHugeOk[d] = ok;
-    c->mtDocChars[d] = chars;
-  }
-  });
-  // Summary-loaded documents past the large tier go to the huge tier; one that holds a feature the
-  // huge tier lacks, or whose state does not fit in device memory, fails alone at load (its header
-  // says why) and the rest of the batch replays.
-  c->mtRefused.clear();
-  std::vector<fmt_mt_doc_result> refusedHdr;
-  auto refuse = [&](uint32_t d, int status) {
-    fmt_mt_doc_result h{};
-    h.status = status;
-    h.fail_seq = b->snapshots[d].seq;
-    h.cur_seq = b->snapshots[d].seq;
-    h.min_seq = b->snapshots[d].min_seq;
-    c->mtRefused.push_back(d);
-    refusedHdr.push_back(h);
-  };
-  if (b->snapshots) {
-    const fmt_kernels::MtCaps big = fmt_kernels::mergeTreeCaps(true);
-    for (uint32_t d = 0; d < n; d++) {
-      const fmt_mt_snapshot_doc& sd = b->snapshots[d];
-      if (!sd.loaded) continue;
-      uint64_t chars = 0;
-      for (uint64_t k = sd.first_seg; k < sd.first_seg + sd.n_header + sd.n_body; k++)
-        chars += b->snapshot_segs[k].len & ~FMT_MT_SEG_MARKER;
-      // (a V1 summary with merge info brings its body as loader-segment ops: they count as loaded)
-      const uint64_t loaded = sd.n_header + sd.n_body + c->mtLoadSegs[d];
-      if (c->mtLoadSegs[d] > 0) chars = c->mtDocChars[d];
-      if (loaded <= big.leaves && chars <= big.chars) continue;
-      if (!c->mtHugeOk[d] || local) {  // (local-client records)
-        refuse(d, FMT_E_UNSUPPORTED);
-        continue;
-      }
-      const int rc = setupHugeDoc(c, b->text_len, b->n_props_ops, d, b->doc_op_offsets[d], b->doc_op_offsets[d + 1],
-                                  c->mtSnapSegs.p + sd.first_seg, sd.n_header, sd.n_body, sd.min_seq, sd.seq,
-                                  FMT_NON_COLLAB_CLIENT, 256,
-                                  c->mtDocChars[d]);
-      if (rc == FMT_E_CAPACITY) refuse(d, FMT_E_CAPACITY);
-      else if (rc != FMT_OK) return rc;
+  c->mtRefused = P.refused;
+  refusedHdr = P.refusedHdr;
+  for (uint32_t d : P.hugeDocs) {
+    const fmt_mt_snapshot_doc& sd = b->snapshots[d];
+    const int rc = setupHugeDoc(c, b->text_len, b->n_props_ops, d, b->doc_op_offsets[d], b->doc_op_offsets[d + 1],
+                                c->mtSnapSegs.p + sd.first_seg, sd.n_header, sd.n_body, sd.min_seq, sd.seq,
+                                FMT_NON_COLLAB_CLIENT, 256, P.docChars[d]);
+    if (rc == FMT_E_CAPACITY) {
+      c->mtRefused.push_back(d);
+      refusedHdr.push_back(fmt_plan::refusalHeader(sd, FMT_E_CAPACITY));
+    } else if (rc != FMT_OK) {
+      return rc;
     }
   }
   for (size_t i = 0; i < c->mtRefused.size(); i++)
-    FMT_HIP(c, hipMemcpyAsync(c->mtHdr.p + c->mtRefused[i], &refusedHdr[i], sizeof(fmt_mt_doc_result), hipMemcpyHostToDevice,
-                              c->stream));
+    FMT_HIP(c, cp(c->mtHdr.p + c->mtRefused[i], &refusedHdr[i], sizeof(fmt_mt_doc_result)));
   c->mtHugeLoaded = static_cast<uint32_t>(c->huge.size());
+  // the small tiers run the other documents from a list
   c->mtUseList = !c->huge.empty() || !c->mtRefused.empty();
   if (c->mtUseList) {
     std::vector<uint8_t> skip(n, 0);
     for (uint32_t d : c->mtRefused) skip[d] = 1;
-    std::vector<uint32_t> small;
     for (uint32_t d = 0; d < n; d++)
       if (c->mtHugeSlot[d] < 0 && !skip[d]) small.push_back(d);
     c->mtNSmall = static_cast<uint32_t>(small.size());
     FMT_HIP(c, c->mtSmallList.reserve(small.size()));
     FMT_HIP(c, cp(c->mtSmallList.p, small.data(), small.size() * sizeof(uint32_t)));
   }
-  if (!c->huge.empty()) {
-    const size_t nh = c->huge.size();
-    FMT_HIP(c, c->hugeStates.reserve(nh));
-    FMT_HIP(c, c->hugeInputs.reserve(nh));
-    FMT_HIP(c, c->hugeOuts.reserve(nh));
-    std::vector<fmt_huge::HugeState> hs(nh);
-    std::vector<fmt_huge::HugeInputs> hi(nh);
-    std::vector<fmt_kernels::HugeOut> ho(nh);
-    for (size_t i = 0; i < nh; i++) {
-      hs[i] = c->huge[i].state;
-      hi[i] = c->huge[i].in;
-      ho[i] = c->huge[i].out;
-    }
-    FMT_HIP(c, cp(c->hugeStates.p, hs.data(), nh * sizeof(fmt_huge::HugeState)));
-    FMT_HIP(c, cp(c->hugeInputs.p, hi.data(), nh * sizeof(fmt_huge::HugeInputs)));
-    FMT_HIP(c, cp(c->hugeOuts.p, ho.data(), nh * sizeof(fmt_kernels::HugeOut)));
-  }
+  const int rc = uploadHuge(c, 0, c->hugeStates, c->hugeInputs, c->hugeOuts);
+  if (rc != FMT_OK) return rc;
   FMT_HIP(c, hipStreamSynchronize(c->stream));
   c->mtLoaded = true;
   return FMT_OK;
@@ -1514,19 +1212,19 @@ int fmt_mt_run(fmt_ctx* c) {
   c->huge.resize(c->mtHugeLoaded);
   fmt_kernels::MtDeviceBatch db{c->mtOps.p, c->mtOffs.p, c->mtDocs, c->mtText.p,
                                 c->mtHasInit ? c->mtInit.p : nullptr, c->mtPropsOff.p, c->mtPropsKv.p, c->mtNProps,
-                                c->mtHasCatchup ? c->mtCuOffs.p : nullptr,
+                                c->mtPlan.hasCatchup() ? c->mtCuOffs.p : nullptr,
                                 c->mtHasSnap ? c->mtSnap.p : nullptr, c->mtHasSnap ? c->mtSnapSegs.p : nullptr,
-                                c->mtHasRmOrder ? c->mtRmOffs.p : nullptr,
+                                c->mtPlan.hasRmOrder() ? c->mtRmOffs.p : nullptr,
                                 c->mtHasSnapInfo ? c->mtSnapInfo.p : nullptr, c->mtHasSnapInfo ? c->mtSnapStamps.p : nullptr,
                                 c->mtHasSnapInfo ? c->mtNSnapSegs : 0u,
                                 c->mtNRelpos ? c->mtRelpos.p : nullptr,
                                 c->mtNRelpos, c->mtMarkerKey,
-                                c->mtHasAdjust ? c->mtAdjTab.p : nullptr,
-                                c->mtLocal ? c->mtLocTab.p : nullptr};
+                                c->mtPlan.anyAdjust ? c->mtAdjTab.p : nullptr,
+                                c->mtPlan.local ? c->mtLocTab.p : nullptr};
   fmt_kernels::MtDeviceOut dout{c->mtHdr.p, c->mtLeaves.p, c->mtChars.p, c->mtProps.p,
-                                c->mtHasCatchup ? c->mtCatchup.p : nullptr, c->mtHasRmOrder ? c->mtRmOrder.p : nullptr,
-                                !c->mtHasRmOrder && !c->mtHasAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr, nullptr, nullptr,
-                                c->mtHasAdjust ? c->mtLegacy.p : nullptr};
+                                c->mtPlan.hasCatchup() ? c->mtCatchup.p : nullptr, c->mtPlan.hasRmOrder() ? c->mtRmOrder.p : nullptr,
+                                !c->mtPlan.hasRmOrder() && !c->mtPlan.anyAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr, nullptr, nullptr,
+                                c->mtPlan.anyAdjust ? c->mtLegacy.p : nullptr};
   FMT_HIP(c, hipMemsetAsync(c->mtEsc.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtEsc2.p, 0, sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipMemsetAsync(c->mtEsc4.p, 0, sizeof(uint32_t), c->stream));
@@ -1534,22 +1232,22 @@ int fmt_mt_run(fmt_ctx* c) {
   if (c->mtDescWords > 0) FMT_HIP(c, hipMemsetAsync(c->mtDesc.p, 0, c->mtDescWords * sizeof(uint32_t), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
   const bool hasHuge = c->mtHugeLoaded > 0, list = c->mtUseList;
-  if (c->mtLocal) {
+  if (c->mtPlan.local) {
     // f4 (round 6): the small tier's local variant over every document (its Adj variant for
     // annotate-adjust batches); those listed in mtEsc replay from their first op in the large tier's
     // local variant below (mergetree_local.hip)
     if (!list || c->mtNSmall > 0)
       FMT_HIP(c, fmt_kernels::launchMergeTreeLocal(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
                                                    c->mtEsc.p, c->mtEsc2.p, c->numCUs, c->stream, c->mtSched.p,
-                                                   c->mtHasAdjust));
+                                                   c->mtPlan.anyAdjust));
   } else if (!list || c->mtNSmall > 0)
     FMT_HIP(c, fmt_kernels::launchMergeTree(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
                                             c->mtEsc.p, c->mtEsc2.p, c->mtEsc3.p, c->mtEsc4.p, c->numCUs, c->stream,
-                                            c->mtObliterate,
-                                            c->mtHasRmOrder, c->mtSched.p, c->mtHasAdjust,
+                                            c->mtPlan.obliterates,
+                                            c->mtPlan.hasRmOrder(), c->mtSched.p, c->mtPlan.anyAdjust,
                                             c->mtDescWords > 0 ? c->mtDesc.p : nullptr));
   if (hasHuge)
-    FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates.p, c->hugeInputs.p, c->hugeOuts.p, c->mtHugeLoaded, c->mtHasAdjust, c->mtHasRmOrder, c->stream));
+    FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates.p, c->hugeInputs.p, c->hugeOuts.p, c->mtHugeLoaded, c->mtPlan.anyAdjust, c->mtPlan.hasRmOrder(), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev1, c->stream));  // device time excludes the host read-back below
   c->timed2 = false;
   // Documents that overflowed the small tier replay again, from their inputs, in the large tier.
@@ -1563,21 +1261,21 @@ int fmt_mt_run(fmt_ctx* c) {
     FMT_HIP(c, c->mtBigLeaves.reserve(static_cast<size_t>(nEsc) * big.leaves));
     FMT_HIP(c, c->mtBigChars.reserve(static_cast<size_t>(nEsc) * big.chars));
     FMT_HIP(c, c->mtBigProps.reserve(static_cast<size_t>(nEsc) * big.props));
-    if (c->mtHasAdjust) FMT_HIP(c, c->mtBigLegacy.reserve(static_cast<size_t>(nEsc) * big.leaves));
+    if (c->mtPlan.anyAdjust) FMT_HIP(c, c->mtBigLegacy.reserve(static_cast<size_t>(nEsc) * big.leaves));
     // every batch but a local one: a document the large tier is about to outgrow leaves a checkpoint
     // for the huge tier (huge_ckpt.h) instead of failing; without the slab it restarts there from its
     // first op
-    const bool hugeCk = !c->mtLocal &&
+    const bool hugeCk = !c->mtPlan.local &&
                         c->mtHugeCk.reserve(static_cast<size_t>(nEsc) * fmt_ckpt::kWords) == hipSuccess;
     if (!hugeCk) (void)hipGetLastError();
     fmt_kernels::MtDeviceOut bout{c->mtHdr.p, c->mtBigLeaves.p, c->mtBigChars.p, c->mtBigProps.p,
-                                  c->mtHasCatchup ? c->mtCatchup.p : nullptr, c->mtHasRmOrder ? c->mtRmOrder.p : nullptr,
-                                  c->mtObliterate && !c->mtHasRmOrder && !c->mtHasAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr,
-                                  !c->mtHasRmOrder ? c->mtLeaves.p : nullptr, !c->mtHasRmOrder ? c->mtChars.p : nullptr,
-                                  c->mtHasAdjust ? c->mtBigLegacy.p : nullptr, hugeCk ? c->mtHugeCk.p : nullptr};
+                                  c->mtPlan.hasCatchup() ? c->mtCatchup.p : nullptr, c->mtPlan.hasRmOrder() ? c->mtRmOrder.p : nullptr,
+                                  c->mtPlan.obliterates && !c->mtPlan.hasRmOrder() && !c->mtPlan.anyAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr,
+                                  !c->mtPlan.hasRmOrder() ? c->mtLeaves.p : nullptr, !c->mtPlan.hasRmOrder() ? c->mtChars.p : nullptr,
+                                  c->mtPlan.anyAdjust ? c->mtBigLegacy.p : nullptr, hugeCk ? c->mtHugeCk.p : nullptr};
     FMT_HIP(c, hipEventRecord(c->ev2, c->stream));
-    FMT_HIP(c, fmt_kernels::launchMergeTreeLarge(db, bout, c->mtEsc.p + 1, nEsc, c->numCUs, c->stream, c->mtObliterate,
-                                                 c->mtHasRmOrder, c->mtSched.p + 2, c->mtHasAdjust, c->mtLocal));
+    FMT_HIP(c, fmt_kernels::launchMergeTreeLarge(db, bout, c->mtEsc.p + 1, nEsc, c->numCUs, c->stream, c->mtPlan.obliterates,
+                                                 c->mtPlan.hasRmOrder(), c->mtSched.p + 2, c->mtPlan.anyAdjust, c->mtPlan.local));
     FMT_HIP(c, hipEventRecord(c->ev3, c->stream));
     c->timed2 = true;
     std::vector<uint32_t> list(nEsc);
@@ -1595,8 +1293,8 @@ int fmt_mt_run(fmt_ctx* c) {
     }
     FMT_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < nEsc; i++) {
-      if ((hb[i].status == FMT_E_CAPACITY || hb[i].status == fmt_ckpt::kStatusHuge) && c->mtHugeOk[list[i]] &&
-          c->mtHugeSlot[list[i]] < 0 && !c->mtLocal) {
+      if ((hb[i].status == FMT_E_CAPACITY || hb[i].status == fmt_ckpt::kStatusHuge) && c->mtHugeSlot[list[i]] < 0 &&
+          !c->mtPlan.local) {
         grow.push_back(list[i]);
         growSlot.push_back(hb[i].status == fmt_ckpt::kStatusHuge ? static_cast<int32_t>(i) : -1);
       }
@@ -1604,7 +1302,7 @@ int fmt_mt_run(fmt_ctx* c) {
     if (!grow.empty()) {
       FMT_HIP(c, c->mtStartSegDev.reserve(grow.size()));
       std::vector<fmt_mt_snapshot_seg> starts(grow.size());
-      for (size_t i = 0; i < grow.size(); i++) starts[i] = c->mtStartSeg[grow[i]];
+      for (size_t i = 0; i < grow.size(); i++) starts[i] = c->mtPlan.startSeg[grow[i]];
       FMT_HIP(c, hipMemcpyAsync(c->mtStartSegDev.p, starts.data(), grow.size() * sizeof(fmt_mt_snapshot_seg),
                                 hipMemcpyHostToDevice, c->stream));
       // (a document whose huge-tier state does not fit in device memory keeps the large tier's
@@ -1615,11 +1313,11 @@ int fmt_mt_run(fmt_ctx* c) {
         int rc;
         if (c->mtSnapHost.size() > d && c->mtSnapHost[d].loaded) {
           const fmt_mt_snapshot_doc& sd = c->mtSnapHost[d];
-          rc = setupHugeDoc(c, c->mtTextLen, c->mtNPropsOps, d, o0, o1, c->mtSnapSegs.p + sd.first_seg, sd.n_header,
-                            sd.n_body, sd.min_seq, sd.seq, FMT_NON_COLLAB_CLIENT, 1024, c->mtDocChars[d]);
+          rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtSnapSegs.p + sd.first_seg, sd.n_header,
+                            sd.n_body, sd.min_seq, sd.seq, FMT_NON_COLLAB_CLIENT, 1024, c->mtPlan.docChars[d]);
         } else {
-          rc = setupHugeDoc(c, c->mtTextLen, c->mtNPropsOps, d, o0, o1, c->mtStartSegDev.p + i, starts[i].len > 0 ? 1 : 0,
-                            0, 0, 0, FMT_LOCAL_CLIENT, 1024, c->mtDocChars[d]);
+          rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtStartSegDev.p + i, starts[i].len > 0 ? 1 : 0,
+                            0, 0, 0, FMT_LOCAL_CLIENT, 1024, c->mtPlan.docChars[d]);
         }
         if (rc != FMT_OK && rc != FMT_E_CAPACITY) return rc;
         if (growSlot[i] >= 0) {
@@ -1639,24 +1337,11 @@ int fmt_mt_run(fmt_ctx* c) {
       }
       const size_t ng = c->huge.size() - c->mtHugeLoaded;
       if (ng > 0) {
-      FMT_HIP(c, c->hugeStates2.reserve(ng));
-      FMT_HIP(c, c->hugeInputs2.reserve(ng));
-      FMT_HIP(c, c->hugeOuts2.reserve(ng));
-      std::vector<fmt_huge::HugeState> hs(ng);
-      std::vector<fmt_huge::HugeInputs> hi(ng);
-      std::vector<fmt_kernels::HugeOut> ho(ng);
-      for (size_t i = 0; i < ng; i++) {
-        const auto& H = c->huge[c->mtHugeLoaded + i];
-        hs[i] = H.state;
-        hi[i] = H.in;
-        ho[i] = H.out;
-      }
-      FMT_HIP(c, hipMemcpyAsync(c->hugeStates2.p, hs.data(), ng * sizeof(fmt_huge::HugeState), hipMemcpyHostToDevice, c->stream));
-      FMT_HIP(c, hipMemcpyAsync(c->hugeInputs2.p, hi.data(), ng * sizeof(fmt_huge::HugeInputs), hipMemcpyHostToDevice, c->stream));
-      FMT_HIP(c, hipMemcpyAsync(c->hugeOuts2.p, ho.data(), ng * sizeof(fmt_kernels::HugeOut), hipMemcpyHostToDevice, c->stream));
-      FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates2.p, c->hugeInputs2.p, c->hugeOuts2.p, static_cast<uint32_t>(ng),
-                                             c->mtHasAdjust, c->mtHasRmOrder, c->stream));
-      FMT_HIP(c, hipStreamSynchronize(c->stream));
+        const int rc = uploadHuge(c, c->mtHugeLoaded, c->hugeStates2, c->hugeInputs2, c->hugeOuts2);
+        if (rc != FMT_OK) return rc;
+        FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates2.p, c->hugeInputs2.p, c->hugeOuts2.p, static_cast<uint32_t>(ng),
+                                               c->mtPlan.anyAdjust, c->mtPlan.hasRmOrder(), c->stream));
+        FMT_HIP(c, hipStreamSynchronize(c->stream));
       }
       c->mtGrown = static_cast<uint32_t>(ng);
     }
@@ -1667,12 +1352,12 @@ int fmt_mt_run(fmt_ctx* c) {
   c->stats.docs = c->mtDocs;
   // Algorithmic bytes: every op record and every inserted UTF-16 unit read once; results written
   // (headers + leaves + chars + prop sets) are added by fmt_mt_fetch_headers once sizes are known.
-  c->stats.bytes_read = c->mtNOps * sizeof(fmt_mt_op) + (c->mtInsertChars + c->mtInitChars) * 2 +
+  c->stats.bytes_read = c->mtNOps * sizeof(fmt_mt_op) + (c->mtPlan.insertChars + c->mtPlan.initChars) * 2 +
                         (c->mtDocs + 1ull) * sizeof(uint64_t);
   c->stats.bytes_written = static_cast<uint64_t>(c->mtDocs) * sizeof(fmt_mt_doc_result);
   // compact + small tier (no remove-order recording) or small tier alone, then the large tier when it ran
   // (+1: the huge-tier pass over documents that outgrew the large tier, after the timed events)
-  c->stats.launches = (!c->mtHasRmOrder ? 2 : 1) + (nEsc > 0 ? 1 : 0) + (c->mtGrown > 0 ? 1 : 0);
+  c->stats.launches = (!c->mtPlan.hasRmOrder() ? 2 : 1) + (nEsc > 0 ? 1 : 0) + (c->mtGrown > 0 ? 1 : 0);
   c->mtRan = true;
   return FMT_OK;
 }
@@ -2024,7 +1709,7 @@ void docViews(const fmt_ctx* c, std::vector<fmt_kernels::SumView>& views) {
     const int32_t hs = d < c->mtHugeSlot.size() ? c->mtHugeSlot[d] : -1;
     if (hs >= 0) {
       const fmt_kernels::HugeOut& O = c->huge[static_cast<size_t>(hs)].out;
-      views[d] = {O.leaves, O.chars, O.props, c->mtHasAdjust ? O.legacy : nullptr, O.cls, O.leavesHi};
+      views[d] = {O.leaves, O.chars, O.props, c->mtPlan.anyAdjust ? O.legacy : nullptr, O.cls, O.leavesHi};
     } else {
       const int32_t slot = d < c->mtBigSlot.size() ? c->mtBigSlot[d] : -1;
       const fmt_kernels::MtCaps caps = fmt_kernels::mergeTreeCaps(slot >= 0);
@@ -2032,7 +1717,7 @@ void docViews(const fmt_ctx* c, std::vector<fmt_kernels::SumView>& views) {
       views[d] = {(slot >= 0 ? c->mtBigLeaves.p : c->mtLeaves.p) + at * caps.leaves,
                   (slot >= 0 ? c->mtBigChars.p : c->mtChars.p) + at * caps.chars,
                   (slot >= 0 ? c->mtBigProps.p : c->mtProps.p) + at * caps.props,
-                  c->mtHasAdjust ? (slot >= 0 ? c->mtBigLegacy.p : c->mtLegacy.p) + at * caps.leaves : nullptr};
+                  c->mtPlan.anyAdjust ? (slot >= 0 ? c->mtBigLegacy.p : c->mtLegacy.p) + at * caps.leaves : nullptr};
     }
   }
 }
@@ -2127,15 +1812,15 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
   std::vector<const fmt_mt_propset*> propsHost(nd);
   for (uint32_t d = 0; d < nd; d++) propsHost[d] = c->sumHostProps.p + propOff[d];
   // computed annotate-adjust numbers of the documents that have any
-  std::vector<std::vector<double>> docNums(c->mtHasAdjust ? nd : 0);
-  if (c->mtHasAdjust) {
+  std::vector<std::vector<double>> docNums(c->mtPlan.anyAdjust ? nd : 0);
+  if (c->mtPlan.anyAdjust) {
     std::vector<uint32_t> cnt(nd);
     FMT_HIP(c, hipMemcpyAsync(cnt.data(), c->mtNumCount.p, nd * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     FMT_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t d = 0; d < nd; d++) {
       docNums[d].resize(cnt[d]);
       if (cnt[d])
-        FMT_HIP(c, hipMemcpyAsync(docNums[d].data(), c->mtNums.p + c->mtNumOffsHost[d], cnt[d] * sizeof(double),
+        FMT_HIP(c, hipMemcpyAsync(docNums[d].data(), c->mtNums.p + c->mtPlan.numOffs[d], cnt[d] * sizeof(double),
                                   hipMemcpyDeviceToHost, c->stream));
     }
   }
@@ -2157,7 +1842,7 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
           c->sumStatus[d] = static_cast<int32_t>(o.status);
           continue;
         }
-        const std::vector<double>* nums = c->mtHasAdjust ? &docNums[d] : nullptr;
+        const std::vector<double>* nums = c->mtPlan.anyAdjust ? &docNums[d] : nullptr;
         // value id v names values[vBase + v] (document-local ids: v <= vCount)
         const uint32_t vBase = c->mtValueBaseHost.empty() ? 0u : c->mtValueBaseHost[d];
         const uint64_t vEnd = c->mtValueBaseHost.empty() ? nValues : std::min<uint64_t>(nValues, c->mtValueBaseHost[d + 1] + 1ull);
@@ -2207,7 +1892,7 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
   if (c == nullptr || !c->mtLoaded || !c->mtRan || (nKeys && keys == nullptr) || (nValues && values == nullptr) ||
       docClientOffs == nullptr || (docClientOffs[c->mtDocs] && clientNames == nullptr))
     return setErr(c, FMT_E_USAGE, "fmt_mt_summarize_v1: bad arguments, or no fmt_mt_run since the load");
-  if (c->mtLocal)
+  if (c->mtPlan.local)
     return setErr(c, FMT_E_UNSUPPORTED, "fmt_mt_summarize_v1: the batch holds local-client records (pending stamps have no SnapshotV1 form)");
   using clk = std::chrono::steady_clock;
   FMT_HIP(c, hipSetDevice(c->device));
@@ -2245,7 +1930,7 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
   std::vector<uint64_t> propOff(nd + 1ull, 0), rmOff(nd + 1ull, 0);
   for (uint32_t d = 0; d < nd; d++) {
     const bool ok = hdr[d].status == FMT_OK;
-    const uint64_t slab = c->mtHasRmOrder ? c->mtRmOffsHost[d + 1] - c->mtRmOffsHost[d] : 0;
+    const uint64_t slab = c->mtPlan.hasRmOrder() ? c->mtPlan.rmOffs[d + 1] - c->mtPlan.rmOffs[d] : 0;
     propOff[d + 1] = propOff[d] + (ok ? hdr[d].n_props : 0u);
     rmOff[d + 1] = rmOff[d] + (ok ? std::min<uint64_t>(hdr[d].n_rm_order, slab) : 0u);
   }
@@ -2255,7 +1940,7 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
       sp.push_back({reinterpret_cast<const uint32_t*>(views[d].props), propOff[d] * kPW,
                     static_cast<uint32_t>(propOff[d + 1] - propOff[d]) * kPW, 0u});
     if (rmOff[d + 1] > rmOff[d])
-      sp.push_back({reinterpret_cast<const uint32_t*>(c->mtRmOrder.p + c->mtRmOffsHost[d]), propOff[nd] * kPW + rmOff[d] * kRW,
+      sp.push_back({reinterpret_cast<const uint32_t*>(c->mtRmOrder.p + c->mtPlan.rmOffs[d]), propOff[nd] * kPW + rmOff[d] * kRW,
                     static_cast<uint32_t>(rmOff[d + 1] - rmOff[d]) * kRW, 0u});
   }
   if (!sp.empty()) {
@@ -2281,15 +1966,15 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
   if (rmOff[nd])
     FMT_HIP(c, hipMemcpyAsync(c->v1HostRm.p, c->packed.p + propOff[nd] * kPW, rmOff[nd] * sizeof(fmt_mt_remove_order),
                               hipMemcpyDeviceToHost, c->stream));
-  std::vector<std::vector<double>> docNums(c->mtHasAdjust ? nd : 0);
-  if (c->mtHasAdjust) {  // computed annotate-adjust numbers of the documents that have any
+  std::vector<std::vector<double>> docNums(c->mtPlan.anyAdjust ? nd : 0);
+  if (c->mtPlan.anyAdjust) {  // computed annotate-adjust numbers of the documents that have any
     std::vector<uint32_t> cnt(nd);
     FMT_HIP(c, hipMemcpyAsync(cnt.data(), c->mtNumCount.p, nd * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     FMT_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t d = 0; d < nd; d++) {
       docNums[d].resize(cnt[d]);
       if (cnt[d])
-        FMT_HIP(c, hipMemcpyAsync(docNums[d].data(), c->mtNums.p + c->mtNumOffsHost[d], cnt[d] * sizeof(double),
+        FMT_HIP(c, hipMemcpyAsync(docNums[d].data(), c->mtNums.p + c->mtPlan.numOffs[d], cnt[d] * sizeof(double),
                                   hipMemcpyDeviceToHost, c->stream));
     }
   }
@@ -2314,7 +1999,7 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
           c->v1Status[d] = static_cast<int32_t>(o.status);
           continue;
         }
-        const std::vector<double>* nums = c->mtHasAdjust ? &docNums[d] : nullptr;
+        const std::vector<double>* nums = c->mtPlan.anyAdjust ? &docNums[d] : nullptr;
         const uint32_t vBase = c->mtValueBaseHost.empty() ? 0u : c->mtValueBaseHost[d];
         const uint64_t vEnd = c->mtValueBaseHost.empty() ? nValues : std::min<uint64_t>(nValues, c->mtValueBaseHost[d + 1] + 1ull);
         const fmt_mt_propset* props = c->sumHostProps.p + propOff[d];
@@ -2373,11 +2058,11 @@ int fmt_mt_summary_v1_body(fmt_ctx* c, uint32_t doc, uint32_t k, const char** bo
 int fmt_mt_fetch_catchup(fmt_ctx* c, uint32_t doc, fmt_mt_catchup_range* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_catchup: bad arguments");
-  if (!c->mtHasCatchup) return FMT_OK;
+  if (!c->mtPlan.hasCatchup()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t m = h.n_catchup < cap ? h.n_catchup : cap;
-  if (m) FMT_HIP(c, hipMemcpy(out, c->mtCatchup.p + c->mtCuOffsHost[doc], m * sizeof(fmt_mt_catchup_range), hipMemcpyDeviceToHost));
+  if (m) FMT_HIP(c, hipMemcpy(out, c->mtCatchup.p + c->mtPlan.cuOffs[doc], m * sizeof(fmt_mt_catchup_range), hipMemcpyDeviceToHost));
   return FMT_OK;
 }
 
@@ -2387,14 +2072,14 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
   FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
   offsets[0] = 0;
-  if (!c->mtHasCatchup) {
+  if (!c->mtPlan.hasCatchup()) {
     for (uint32_t d = 0; d < nd; d++) offsets[d + 1] = 0;
     return FMT_OK;
   }
   std::vector<fmt_mt_doc_result> hdr(nd);
   FMT_HIP(c, hipMemcpy(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost));
   for (uint32_t d = 0; d < nd; d++) {
-    const uint64_t slab = c->mtCuOffsHost[d + 1] - c->mtCuOffsHost[d];
+    const uint64_t slab = c->mtPlan.cuOffs[d + 1] - c->mtPlan.cuOffs[d];
     offsets[d + 1] = offsets[d] + std::min<uint64_t>(hdr[d].n_catchup, slab);
   }
   if (out == nullptr) return FMT_OK;
@@ -2406,7 +2091,7 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
   sp.reserve(nd);
   for (uint32_t d = 0; d < nd; d++)
     if (offsets[d + 1] > offsets[d])
-      sp.push_back({reinterpret_cast<const uint32_t*>(c->mtCatchup.p + c->mtCuOffsHost[d]), offsets[d] * kW,
+      sp.push_back({reinterpret_cast<const uint32_t*>(c->mtCatchup.p + c->mtPlan.cuOffs[d]), offsets[d] * kW,
                     static_cast<uint32_t>(offsets[d + 1] - offsets[d]) * kW, 0u});
   if (offsets[nd] == 0) return FMT_OK;
   FMT_HIP(c, c->spans.reserve(sp.size()));
@@ -2421,11 +2106,11 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
-  if (!c->mtHasRmOrder) return FMT_OK;
+  if (!c->mtPlan.hasRmOrder()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t m = h.n_rm_order < cap ? h.n_rm_order : cap;
-  if (m) FMT_HIP(c, hipMemcpy(out, c->mtRmOrder.p + c->mtRmOffsHost[doc], m * sizeof(fmt_mt_remove_order), hipMemcpyDeviceToHost));
+  if (m) FMT_HIP(c, hipMemcpy(out, c->mtRmOrder.p + c->mtPlan.rmOffs[doc], m * sizeof(fmt_mt_remove_order), hipMemcpyDeviceToHost));
   return FMT_OK;
 }
 
@@ -2483,10 +2168,10 @@ int fmt_mt_fetch_numbers(fmt_ctx* c, uint32_t doc, double* out, uint32_t cap, ui
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_numbers: bad arguments");
   uint32_t n = 0;
-  if (c->mtHasAdjust) FMT_HIP(c, hipMemcpy(&n, c->mtNumCount.p + doc, sizeof n, hipMemcpyDeviceToHost));
+  if (c->mtPlan.anyAdjust) FMT_HIP(c, hipMemcpy(&n, c->mtNumCount.p + doc, sizeof n, hipMemcpyDeviceToHost));
   if (nOut) *nOut = n;
   const uint32_t m = n < cap ? n : cap;
-  if (m) FMT_HIP(c, hipMemcpy(out, c->mtNums.p + c->mtNumOffsHost[doc], m * sizeof(double), hipMemcpyDeviceToHost));
+  if (m) FMT_HIP(c, hipMemcpy(out, c->mtNums.p + c->mtPlan.numOffs[doc], m * sizeof(double), hipMemcpyDeviceToHost));
   return FMT_OK;
 }
 
@@ -2495,12 +2180,12 @@ int fmt_mt_fetch_regen(fmt_ctx* c, uint32_t doc, fmt_mt_op* ops, uint32_t capOps
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (ops == nullptr && capOps > 0) || (text == nullptr && capText > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_regen: bad arguments");
   uint32_t cnt[2] = {0, 0};
-  if (c->mtLocal) FMT_HIP(c, hipMemcpy(cnt, c->mtLocRegenCount.p + 2ull * doc, sizeof cnt, hipMemcpyDeviceToHost));
+  if (c->mtPlan.local) FMT_HIP(c, hipMemcpy(cnt, c->mtLocRegenCount.p + 2ull * doc, sizeof cnt, hipMemcpyDeviceToHost));
   if (nOps) *nOps = cnt[0];
   if (nText) *nText = cnt[1];
   const uint32_t m = cnt[0] < capOps ? cnt[0] : capOps, t = cnt[1] < capText ? cnt[1] : capText;
-  if (m) FMT_HIP(c, hipMemcpy(ops, c->mtLocRegen.p + c->mtLocRegenOffsHost[doc], m * sizeof(fmt_mt_op), hipMemcpyDeviceToHost));
-  if (t) FMT_HIP(c, hipMemcpy(text, c->mtLocRegenText.p + c->mtLocRegenTextOffsHost[doc], t * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (m) FMT_HIP(c, hipMemcpy(ops, c->mtLocRegen.p + c->mtPlan.locSlabOffs(fmt_plan::kLocRegen)[doc], m * sizeof(fmt_mt_op), hipMemcpyDeviceToHost));
+  if (t) FMT_HIP(c, hipMemcpy(text, c->mtLocRegenText.p + c->mtPlan.locSlabOffs(fmt_plan::kLocRegenText)[doc], t * sizeof(uint16_t), hipMemcpyDeviceToHost));
   return FMT_OK;
 }
 
@@ -2515,6 +2200,59 @@ int fmt_internal_huge_profile(fmt_ctx* c, uint32_t doc, uint64_t* out) {
 
 // Test hook (not part of fmt.h): the summary formatters' JSON.stringify of a number (jsnum.h).
 int fmt_internal_js_number(double x, char* out, int cap) { return out == nullptr || cap < 0 ? 0 : fmt_json::jsNumber(x, out, cap); }
+
+// Test hook (not part of fmt.h): fmt_mt_load's host half (mt_plan.h planMergeTreeLoad) with the large
+// tier's capacities, no device needed. Returns the plan's status, *err its message (NULL: FMT_OK). The
+// plan goes to a holder the calling thread keeps, and *out / *n_words describe the holder: a refused
+// batch leaves there the plan of the thread's last valid batch, as fmt_mt_load leaves its context. Words
+// 0..5: insertChars, initChars, catchupOps, rmOrderOps, flags (1 obliterates, 2 local, 4 hiClients, 8
+// anyAdjust), number of documents; then 14 arrays, each its length and its elements: cuOffs, rmOffs,
+// numOffs, pmOffs, locOffs, numSorted (the doubles' bits), numSortedId, numSortedOffs, loadSegs, segProps,
+// docChars, startSeg (text, len, props), hugeDocs, refused (doc, status, fail_seq, cur_seq, min_seq; signed
+// values sign-extended). Valid until the calling thread's next call.
+int fmt_internal_mt_plan(const fmt_mt_batch* b, const char** err, const uint64_t** out, uint64_t* nWords) {
+  static thread_local fmt_plan::MtPlan held;
+  static thread_local std::vector<uint64_t> w;
+  if (err == nullptr || out == nullptr || nWords == nullptr) return FMT_E_USAGE;
+  *err = nullptr;
+  const int rc = fmt_plan::planMergeTreeLoad(b, fmt_kernels::mergeTreeCaps(true), held, err);
+  const fmt_plan::MtPlan& P = held;
+  w.assign({P.insertChars, P.initChars, P.catchupOps, P.rmOrderOps,
+            (P.obliterates ? 1ull : 0) | (P.local ? 2ull : 0) | (P.hiClients ? 4ull : 0) | (P.anyAdjust ? 8ull : 0),
+            P.docChars.size()});
+  auto put = [&](const auto& v) {
+    w.push_back(v.size());
+    w.insert(w.end(), v.begin(), v.end());
+  };
+  put(P.cuOffs);
+  put(P.rmOffs);
+  put(P.numOffs);
+  put(P.pmOffs);
+  put(P.locOffs);
+  w.push_back(P.numSorted.size());
+  for (double x : P.numSorted) {
+    uint64_t bits;
+    std::memcpy(&bits, &x, sizeof bits);
+    w.push_back(bits);
+  }
+  put(P.numSortedId);
+  put(P.numSortedOffs);
+  put(P.loadSegs);
+  put(P.segProps);
+  put(P.docChars);
+  w.push_back(P.startSeg.size());
+  for (const fmt_mt_snapshot_seg& sg : P.startSeg) w.insert(w.end(), {sg.text, sg.len, sg.props});
+  put(P.hugeDocs);
+  w.push_back(P.refused.size());
+  for (size_t i = 0; i < P.refused.size(); i++) {
+    const fmt_mt_doc_result& h = P.refusedHdr[i];
+    for (int64_t x : {int64_t{P.refused[i]}, int64_t{h.status}, int64_t{h.fail_seq}, int64_t{h.cur_seq}, int64_t{h.min_seq}})
+      w.push_back(static_cast<uint64_t>(x));
+  }
+  *out = w.data();
+  *nWords = w.size();
+  return rc;
+}
 
 // Test hook (not part of fmt_v1.h): fmt_mt_summarize_v1's host formatter (v1Blobs) over one document
 // given as host arrays, no device needed. segs: n_segs fmt_kernels::SumV1Seg records (kernels.h) and

@@ -345,6 +345,42 @@ def legacy_format(runs, text, propsets, keys, values, min_seq, chunk=10000, numb
     return blobs[0], (blobs[1] if len(blobs) > 1 else None)
 
 
+class MtPlanResult:
+    """What mt_plan read back: `status`, `message` (None: FMT_OK) and the plan of csrc/mt_plan.h MtPlan
+    as attributes (numpy arrays and Python scalars; loc_offs as (6, n_docs + 1) or empty)."""
+
+
+def mt_plan(batch, struct=None) -> MtPlanResult:
+    """fmt_internal_mt_plan: fmt_mt_load's host half over `batch` (validation, slab sizing, routing), no
+    device needed. A refused batch reports its status and message beside the plan of the calling
+    thread's last valid batch. struct: an fmt_mt_batch to plan instead of batch_struct(batch)."""
+    b, keep = (struct, None) if struct is not None else batch_struct(batch)
+    P = ctypes.c_void_p
+    f = lib().fmt_internal_mt_plan
+    f.argtypes = [ctypes.POINTER(FmtMtBatch), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(P),
+                  ctypes.POINTER(ctypes.c_uint64)]
+    err, out, n = ctypes.c_char_p(), P(), ctypes.c_uint64()
+    r = MtPlanResult()
+    r.status = f(ctypes.byref(b), ctypes.byref(err), ctypes.byref(out), ctypes.byref(n))
+    r.message = err.value.decode() if err.value else None
+    w = np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy()
+    r.insert_chars, r.init_chars, r.catchup_ops, r.rm_order_ops, flags, r.n_docs = (int(x) for x in w[:6])
+    r.obliterates, r.local, r.hi_clients, r.any_adjust = (bool(flags & k) for k in (1, 2, 4, 8))
+    at = 6
+    for name in ("cu_offs", "rm_offs", "num_offs", "pm_offs", "loc_offs", "num_sorted", "num_sorted_id",
+                 "num_sorted_offs", "load_segs", "seg_props", "doc_chars", "start_seg", "huge_docs", "refused"):
+        width = {"start_seg": 3, "refused": 5}.get(name, 1)
+        cnt = int(w[at]) * width
+        setattr(r, name, w[at + 1 : at + 1 + cnt])
+        at += 1 + cnt
+    assert at == len(w)
+    r.num_sorted = r.num_sorted.view(np.float64)
+    r.loc_offs = r.loc_offs.reshape(6, -1) if len(r.loc_offs) else r.loc_offs
+    r.start_seg = r.start_seg.reshape(-1, 3)
+    r.refused = r.refused.view(np.int64).reshape(-1, 5)  # doc, status, fail_seq, cur_seq, min_seq
+    return r
+
+
 def capacity():
     a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
     lib().fmt_mt_capacity(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))

@@ -13,6 +13,7 @@
 #endif
 
 #include "../../fluidframework_amd/csrc/huge_engine.h"
+#include "../../fluidframework_amd/csrc/mt_plan.h"
 
 using namespace fmt_huge;
 
@@ -32,27 +33,8 @@ const fmt_mt::AdjustTables* prepareNumbers(const fmt_mt_batch* b) {
   g_numSortedId.clear();
   g_numSortedOffs.clear();
   if (b->adjusts == nullptr || b->value_num == nullptr) return nullptr;
-  auto sortNumbers = [&](uint32_t lo, uint32_t hi, uint32_t base) {
-    std::vector<std::pair<double, uint32_t>> v;
-    for (uint32_t i = lo; i < hi; i++)
-      if (b->value_num[base + i] == b->value_num[base + i]) v.emplace_back(b->value_num[base + i] == 0.0 ? 0.0 : b->value_num[base + i], i);
-    std::stable_sort(v.begin(), v.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    const size_t first = g_numSorted.size();
-    for (const auto& [x, i] : v) {
-      if (g_numSorted.size() > first && g_numSorted.back() == x) continue;
-      g_numSorted.push_back(x);
-      g_numSortedId.push_back(i);
-    }
-  };
-  if (b->doc_value_base != nullptr) {
-    g_numSortedOffs.assign(1, 0u);
-    for (uint32_t d = 0; d < b->n_docs; d++) {
-      sortNumbers(1, b->doc_value_base[d + 1] - b->doc_value_base[d] + 1, b->doc_value_base[d]);
-      g_numSortedOffs.push_back(static_cast<uint32_t>(g_numSorted.size()));
-    }
-  } else {
-    sortNumbers(0, b->n_values, 0);
-  }
+  fmt_plan::prepareSortedNumbers(b->value_num, b->n_values, b->doc_value_base, b->n_docs, g_numSorted, g_numSortedId,
+                                 g_numSortedOffs);
   // every document indexes its own slabs; only the replayed one gets room
   g_nums.assign(kEmuNumCap, 0.0);
   g_numCount.assign(b->n_docs, 0u);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "emu_batch.h"
+#include "../../fluidframework_amd/csrc/mt_plan.h"
 
 // Annotate-adjust state of the last emulated replay (the runtime's number slabs, fixed capacity
 // here): the batch's host numbers sorted for number → id lookups, per-document number tables.
@@ -33,29 +34,9 @@ static void prepareNumbers(const fmt_mt_batch* b) {
   g_nums.clear();
   g_numCount.assign(b->n_docs, 0u);
   if (b->adjusts == nullptr || b->value_num == nullptr) return;
-  // the host numbers ascending with their first value id (runtime.cpp fmt_mt_load): one list, or per
-  // document with local ids when value ids are document-local (doc_value_base)
-  auto sortNumbers = [&](uint32_t lo, uint32_t hi, uint32_t base) {
-    std::vector<std::pair<double, uint32_t>> v;
-    for (uint32_t i = lo; i < hi; i++)
-      if (b->value_num[base + i] == b->value_num[base + i]) v.emplace_back(b->value_num[base + i] == 0.0 ? 0.0 : b->value_num[base + i], i);
-    std::stable_sort(v.begin(), v.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    const size_t first = g_numSorted.size();
-    for (const auto& [x, i] : v) {
-      if (g_numSorted.size() > first && g_numSorted.back() == x) continue;  // the first id of an equal number
-      g_numSorted.push_back(x);
-      g_numSortedId.push_back(i);
-    }
-  };
-  if (b->doc_value_base != nullptr) {
-    g_numSortedOffs.assign(1, 0u);
-    for (uint32_t d = 0; d < b->n_docs; d++) {
-      sortNumbers(1, b->doc_value_base[d + 1] - b->doc_value_base[d] + 1, b->doc_value_base[d]);
-      g_numSortedOffs.push_back(static_cast<uint32_t>(g_numSorted.size()));
-    }
-  } else {
-    sortNumbers(0, b->n_values, 0);
-  }
+  // the host numbers ascending with their first value id, as fmt_mt_load prepares them
+  fmt_plan::prepareSortedNumbers(b->value_num, b->n_values, b->doc_value_base, b->n_docs, g_numSorted, g_numSortedId,
+                                 g_numSortedOffs);
   g_nums.assign(static_cast<size_t>(b->n_docs) * kEmuNumCap, 0.0);
   g_numOffs.resize(b->n_docs + 1ull);
   for (uint32_t d = 0; d <= b->n_docs; d++) g_numOffs[d] = static_cast<uint64_t>(d) * kEmuNumCap;

@@ -31,7 +31,7 @@ def emu_lib():
     global _emu
     if _emu is None:
         src = os.path.join(HERE, "emu", "mt_emu.cpp")
-        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
+        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h", "mt_plan.h")]
         if not os.path.exists(EMU_PATH) or os.path.getmtime(EMU_PATH) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(EMU_PATH), exist_ok=True)
             _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], EMU_PATH, src)
@@ -64,7 +64,7 @@ def huge_emu_lib(tiny_groups=False):
         name = "libhuge_emu_tiny.so" if tiny_groups else "libhuge_emu.so"
         path = os.path.join(HERE, "_build", name)
         src = os.path.join(HERE, "emu", "huge_emu.cpp")
-        deps = [src, os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("huge_engine.h", "wave.h", "adjust.h", "huge_ckpt.h")]
+        deps = [src, os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("huge_engine.h", "wave.h", "adjust.h", "huge_ckpt.h", "mt_plan.h")]
         if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(path), exist_ok=True)
             extra = ["-DFMT_HUGE_SLOTCAP=16", "-DFMT_HUGE_FILL=8"] if tiny_groups else []

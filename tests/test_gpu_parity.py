@@ -781,6 +781,18 @@ def test_mt_document_local_value_ids_on_gpu(orc, engine, adjust):
     batch = marker_batch(200, 1200, seed=3) if not adjust else marker_batch(120, 900, seed=5, adjust=True)
     assert batch.value_base is not None
     engine.mt_load(batch)
+    if adjust:
+        # a batch that validation refuses after the doc_value_base check (batch-global ids, adjusts
+        # without value_num) leaves the loaded batch as it was, its value bases included
+        import ctypes
+        import dataclasses
+
+        from fluidframework_amd import native
+
+        bad, keep = native.batch_struct(dataclasses.replace(batch, value_base=None))
+        bad.value_num = None
+        assert engine.L.fmt_mt_load(engine.h, ctypes.byref(bad)) == native.FMT_E_USAGE
+        assert b"adjusts need value_num" in engine.L.fmt_last_error(engine.h)
     engine.mt_run()
     hdrs = engine.mt_headers()
     assert (hdrs["status"] == 0).all()

@@ -17,7 +17,7 @@ SRCS = [os.path.join(HERE, "san", "san_check.cpp"), os.path.join(HERE, "emu", "m
        [os.path.join(REPO, "oracle", f) for f in ("mergetree.cpp", "map.cpp", "capi.cpp")] + \
        [os.path.join(REPO, "fluidframework_amd", "csrc", "gen", "fmtgen.cpp")]
 DEPS = SRCS + [os.path.join(REPO, "include", "fmt.h"), os.path.join(HERE, "emu", "emu_batch.h")] + \
-       [os.path.join(REPO, "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h")] + \
+       [os.path.join(REPO, "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "mt_plan.h")] + \
        [os.path.join(REPO, "oracle", f) for f in ("mergetree.hpp", "common.hpp", "map.hpp")]
 
 

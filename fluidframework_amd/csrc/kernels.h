@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fmt.h"
+#include "map_plan.h"
 #include "mt_bind.h"
 
 namespace fmt_kernels {
@@ -16,8 +17,27 @@ bool mapLwwNeedsScratch(uint32_t keyBound);
 size_t mapSparseLdsBytes();
 hipError_t launchMapSparse(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
                            fmt_map_entry* out, uint32_t* counts, int* error, int numCUs, hipStream_t stream);
+// The same kernel, its tracking instantiation: every document it refuses is also appended to
+// overflow ([0] = count, zeroed by the caller; then the document ids, in no order).
+hipError_t launchMapSparseTracked(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
+                                  fmt_map_entry* out, uint32_t* counts, int* error, uint32_t* overflow, int numCUs,
+                                  hipStream_t stream);
 hipError_t launchMapSparsePack(const fmt_map_entry* in, const uint64_t* offsets, const uint32_t* counts,
                                const uint64_t* packedOff, uint32_t nDocs, fmt_map_entry* packed, hipStream_t stream);
+// ---- SharedMap sparse path, HBM tier (map_sparse_large.hip; layout and sizes: map_plan.h)
+struct MapLargeArgs {
+  const fmt_map_op* ops;                 // the staged batch
+  const fmt_plan::MapLargeDoc* docs;     // the overflowing documents
+  const uint32_t* tileDoc;               // tile -> index into docs
+  const uint32_t* tileFirst;             // tile -> first op within the document
+  uint32_t* scratch;                     // MapLargePlan::words() words
+  fmt_map_entry* out;                    // as launchMapSparse
+  uint32_t* counts;
+  int* error;
+  uint64_t slots, tileCountAt, clearAt;  // MapLargePlan::slots / tileCountAt() / clearAt()
+  uint32_t nDocs, nTiles, keyBound;
+};
+hipError_t launchMapLarge(const MapLargeArgs& a, int numCUs, hipStream_t stream, uint32_t* launches);
 // ---- SharedMap local-client pending state (map_pending.hip)
 size_t mapPendingScratchBytes(uint64_t nEvents);
 hipError_t launchMapPending(const fmt_map_local_op* events, const uint64_t* evOffs, const fmt_map_entry* seqEntries,

@@ -135,9 +135,19 @@ __device__ __forceinline__ bool spClaim(SpWave* w, const SpOp (&op)[R], uint32_t
   return false;
 }
 
+// A document this kernel refuses (the two branches that raise error bit 2) is also listed for the HBM
+// tier (map_sparse_large.hip) by the Track instantiation: count 0 alone cannot tell it from an empty
+// map. fmt_map_run_sparse launches Track = false, which has no such code and never reads `overflow`.
+template <bool Track>
+__device__ __forceinline__ void spRefused(uint32_t* overflow, uint32_t doc) {
+  if constexpr (Track) overflow[1 + atomicAdd(&overflow[0], 1u)] = doc;
+}
+
+template <bool Track>
 __global__ __launch_bounds__(64 * kSpWaves) __attribute__((amdgpu_waves_per_eu(2))) void mapSparseKernel(
     const fmt_map_op* __restrict__ ops, const uint64_t* __restrict__ offsets, uint32_t nDocs, uint32_t keyBound,
-    fmt_map_entry* __restrict__ out, uint32_t* __restrict__ counts, int* __restrict__ error) {
+    fmt_map_entry* __restrict__ out, uint32_t* __restrict__ counts, int* __restrict__ error,
+    uint32_t* __restrict__ overflow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -208,6 +218,7 @@ __global__ __launch_bounds__(64 * kSpWaves) __attribute__((amdgpu_waves_per_eu(2
       if (lane == 0) {
         counts[doc] = 0;
         atomicOr(error, 2);
+        spRefused<Track>(overflow, doc);
       }
     } else {
       // table size: >= 2 slots per op after the last clear (load <= 1/2), 64 .. 2048
@@ -404,7 +415,10 @@ __global__ __launch_bounds__(64 * kSpWaves) __attribute__((amdgpu_waves_per_eu(2
       }
       if (full) {  // more distinct keys than the table holds: reported, no entries
         live = 0;
-        if (lane == 0) atomicOr(error, 2);
+        if (lane == 0) {
+          atomicOr(error, 2);
+          spRefused<Track>(overflow, doc);
+        }
       }
       if (lane == 0) counts[doc] = live;
       spSync();
@@ -431,19 +445,32 @@ __global__ void mapSparsePackKernel(const fmt_map_entry* __restrict__ in, const 
 
 size_t mapSparseLdsBytes() { return sizeof(SpWave) * kSpWaves; }
 
-hipError_t launchMapSparse(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
-                           fmt_map_entry* out, uint32_t* counts, int* error, int numCUs, hipStream_t stream) {
+template <bool Track>
+static hipError_t launchSparse(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
+                               fmt_map_entry* out, uint32_t* counts, int* error, uint32_t* overflow, int numCUs,
+                               hipStream_t stream) {
   const size_t lds = mapSparseLdsBytes();
   int blocksPerCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, mapSparseKernel, 64 * kSpWaves, lds) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, mapSparseKernel<Track>, 64 * kSpWaves, lds) != hipSuccess ||
       blocksPerCU <= 0)
     blocksPerCU = 1;
   const uint32_t wanted = (nDocs + kSpWaves - 1) / kSpWaves;
   const uint32_t cap = static_cast<uint32_t>(numCUs * blocksPerCU);
   const uint32_t grid = wanted < cap ? (wanted > 0 ? wanted : 1) : cap;
-  hipLaunchKernelGGL(mapSparseKernel, dim3(grid), dim3(64 * kSpWaves), lds, stream, ops, offsets, nDocs, keyBound, out,
-                     counts, error);
+  hipLaunchKernelGGL(mapSparseKernel<Track>, dim3(grid), dim3(64 * kSpWaves), lds, stream, ops, offsets, nDocs, keyBound,
+                     out, counts, error, overflow);
   return hipGetLastError();
+}
+
+hipError_t launchMapSparse(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
+                           fmt_map_entry* out, uint32_t* counts, int* error, int numCUs, hipStream_t stream) {
+  return launchSparse<false>(ops, offsets, nDocs, keyBound, out, counts, error, nullptr, numCUs, stream);
+}
+
+hipError_t launchMapSparseTracked(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
+                                  fmt_map_entry* out, uint32_t* counts, int* error, uint32_t* overflow, int numCUs,
+                                  hipStream_t stream) {
+  return launchSparse<true>(ops, offsets, nDocs, keyBound, out, counts, error, overflow, numCUs, stream);
 }
 
 hipError_t launchMapSparsePack(const fmt_map_entry* in, const uint64_t* offsets, const uint32_t* counts,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/fmt.h"
+#include "../../include/fmt_map_tiered.h"
 #include "../../include/fmt_v1.h"
 #include "huge_engine.h"
 #include "jsnum.h"
@@ -129,6 +130,11 @@ struct fmt_ctx {
   bool mapSparse = false;
   bool mapSparseRan = false;
   std::vector<uint64_t> mapOffsHost;  // the staged batch's doc_op_offsets
+  // sparse path, HBM tier (fmt_map_run_sparse_tiered): the LDS tier's overflow list ([0] = count),
+  // the plan of the last run that had one (map_plan.h) and its device copies, the tables
+  DevBuf<uint32_t> mapOvf, mapLgTiles, mapLgScratch;
+  DevBuf<fmt_plan::MapLargeDoc> mapLgDocs;
+  fmt_plan::MapLargePlan mapLgPlan;
   // SharedMap local-client pending state (fmt_map_pending_run): events, per-event scratch, the
   // optimistic entries at mapPendBase[d] = op offset + event offset of the document
   DevBuf<fmt_map_local_op> mapEv;
@@ -407,6 +413,10 @@ void fmt_close(fmt_ctx* c) {
   c->mapPendCounts.release();
   c->mapPendStatus.release();
   c->mapCounts.release();
+  c->mapOvf.release();
+  c->mapLgTiles.release();
+  c->mapLgScratch.release();
+  c->mapLgDocs.release();
   c->mapPackedOff.release();
   c->errWord.release();
   c->mtOps.release();
@@ -585,6 +595,79 @@ int fmt_map_run_sparse(fmt_ctx* c) {
   c->stats.launches = 1;
   c->mapSparseRan = true;
   c->mapPendRan = false;
+  return FMT_OK;
+}
+
+// The LDS tier with its refusals listed, then the HBM tier (map_sparse_large.hip) over the list.
+int fmt_map_run_sparse_tiered(fmt_ctx* c) {
+  if (c == nullptr || !c->mapLoaded || !c->mapSparse)
+    return setErr(c, FMT_E_USAGE, "fmt_map_run_sparse_tiered before fmt_map_load_sparse");
+  FMT_HIP(c, hipSetDevice(c->device));
+  FMT_HIP(c, c->mapOvf.reserve(c->mapDocs + 1ull));
+  FMT_HIP(c, hipMemsetAsync(c->errWord.p, 0, sizeof(int), c->stream));
+  FMT_HIP(c, hipMemsetAsync(c->mapOvf.p, 0, sizeof(uint32_t), c->stream));
+  FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
+  FMT_HIP(c, fmt_kernels::launchMapSparseTracked(c->mapOps.p, c->mapOffs.p, c->mapDocs, c->mapKeyBound, c->mapEntries.p,
+                                                 c->mapCounts.p, c->errWord.p, c->mapOvf.p, c->numCUs, c->stream));
+  FMT_HIP(c, hipEventRecord(c->ev1, c->stream));
+  c->timed = true;
+  c->timed2 = false;
+  c->stats = fmt_stats{};
+  c->stats.ops = c->mapNOps;
+  c->stats.docs = c->mapDocs;
+  c->stats.bytes_read = c->mapNOps * sizeof(fmt_map_op) + (c->mapDocs + 1ull) * sizeof(uint64_t);
+  c->stats.bytes_written = static_cast<uint64_t>(c->mapDocs) * sizeof(uint32_t);  // + entries, at fetch
+  c->stats.launches = 1;
+  c->mapSparseRan = true;  // (the LDS tier's documents are valid whatever becomes of the rest)
+  c->mapPendRan = false;
+  uint32_t nOvf = 0;
+  FMT_HIP(c, hipMemcpyAsync(&nOvf, c->mapOvf.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  if (nOvf == 0) return FMT_OK;
+  std::vector<uint32_t> ovf(nOvf);
+  FMT_HIP(c, hipMemcpy(ovf.data(), c->mapOvf.p + 1, nOvf * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::sort(ovf.begin(), ovf.end());
+  fmt_plan::MapLargePlan& P = c->mapLgPlan;
+  if (const char* why = fmt_plan::planMapLarge(c->mapOffsHost.data(), c->mapDocs, ovf.data(), nOvf, P))
+    return setErr(c, FMT_E_CAPACITY, why);
+  const size_t nTiles = P.tileDoc.size();
+  if (c->mapLgScratch.reserve(P.words()) != hipSuccess || c->mapLgDocs.reserve(nOvf) != hipSuccess ||
+      c->mapLgTiles.reserve(2 * nTiles) != hipSuccess) {
+    (void)hipGetLastError();
+    char m[160];
+    std::snprintf(m, sizeof m, "no device memory for the HBM tier of %u document(s): %llu bytes of tables; they stay refused",
+                  nOvf, static_cast<unsigned long long>(P.scratchBytes()));
+    return setErr(c, FMT_E_DEVICE, m);
+  }
+  FMT_HIP(c, hipMemcpyAsync(c->mapLgDocs.p, P.docs.data(), nOvf * sizeof(fmt_plan::MapLargeDoc), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipMemcpyAsync(c->mapLgTiles.p, P.tileDoc.data(), nTiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  FMT_HIP(c, hipMemcpyAsync(c->mapLgTiles.p + nTiles, P.tileFirst.data(), nTiles * sizeof(uint32_t), hipMemcpyHostToDevice,
+                            c->stream));
+  fmt_kernels::MapLargeArgs a{};
+  a.ops = c->mapOps.p;
+  a.docs = c->mapLgDocs.p;
+  a.tileDoc = c->mapLgTiles.p;
+  a.tileFirst = c->mapLgTiles.p + nTiles;
+  a.scratch = c->mapLgScratch.p;
+  a.out = c->mapEntries.p;
+  a.counts = c->mapCounts.p;
+  a.error = c->errWord.p;
+  a.slots = P.slots;
+  a.tileCountAt = P.tileCountAt();
+  a.clearAt = P.clearAt();
+  a.nDocs = nOvf;
+  a.nTiles = static_cast<uint32_t>(nTiles);
+  a.keyBound = c->mapKeyBound;
+  uint32_t launches = 0;
+  FMT_HIP(c, hipEventRecord(c->ev2, c->stream));
+  FMT_HIP(c, fmt_kernels::launchMapLarge(a, c->numCUs, c->stream, &launches));
+  FMT_HIP(c, hipEventRecord(c->ev3, c->stream));
+  c->timed2 = true;
+  FMT_HIP(c, hipStreamSynchronize(c->stream));  // (the plan's host arrays are read by the copies above)
+  // the passes' streamed traffic (map_sparse_large.hip); the table atomics and probes are not counted
+  c->stats.bytes_read += P.ops * (2 * sizeof(fmt_map_op) + 3 * 4) + nTiles * (2 * 8 + 2 * 4);
+  c->stats.bytes_written += P.slots * 20 + P.ops * 4 + nTiles * 8 + nOvf * 4ull;
+  c->stats.launches += launches;
   return FMT_OK;
 }
 
@@ -2252,6 +2335,33 @@ int fmt_internal_mt_plan(const fmt_mt_batch* b, const char** err, const uint64_t
   *out = w.data();
   *nWords = w.size();
   return rc;
+}
+
+// Test hook (not part of fmt.h): the HBM map tier's host half (map_plan.h planMapLarge) over a batch's
+// doc_op_offsets and a list of overflowing documents, no device needed. Returns FMT_OK, or FMT_E_USAGE with
+// *err the reason. Words 0..11: tile size, scratch bytes, slots, ops, then the region starts in words (key,
+// first, D, last, value, op slot, tile counts, last clear); then three arrays, each its length and its
+// elements: documents (doc, n_ops, slots, table_off, op_slot_off, first_tile, n_tiles, shift each), tileDoc,
+// tileFirst. Valid until the calling thread's next call.
+int fmt_internal_map_large_plan(const uint64_t* docOpOffsets, uint32_t nDocs, const uint32_t* overflow, uint32_t nOverflow,
+                                const char** err, const uint64_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint64_t> w;
+  if (docOpOffsets == nullptr || (nOverflow && overflow == nullptr) || err == nullptr || out == nullptr || nWords == nullptr)
+    return FMT_E_USAGE;
+  fmt_plan::MapLargePlan P;
+  *err = fmt_plan::planMapLarge(docOpOffsets, nDocs, overflow, nOverflow, P);
+  w.assign({fmt_plan::kMapLargeTile, P.scratchBytes(), P.slots, P.ops, P.keyAt(), P.firstAt(), P.delAt(), P.lastAt(),
+            P.valueAt(), P.opSlotAt(), P.tileCountAt(), P.clearAt()});
+  w.push_back(P.docs.size());
+  for (const fmt_plan::MapLargeDoc& d : P.docs)
+    w.insert(w.end(), {d.doc, d.nOps, uint64_t{d.mask} + 1, d.tableOff, d.opSlotOff, d.firstTile, d.nTiles, d.shift});
+  w.push_back(P.tileDoc.size());
+  w.insert(w.end(), P.tileDoc.begin(), P.tileDoc.end());
+  w.push_back(P.tileFirst.size());
+  w.insert(w.end(), P.tileFirst.begin(), P.tileFirst.end());
+  *out = w.data();
+  *nWords = w.size();
+  return *err ? FMT_E_USAGE : FMT_OK;
 }
 
 // Test hook (not part of fmt_v1.h): fmt_mt_summarize_v1's host formatter (v1Blobs) over one document

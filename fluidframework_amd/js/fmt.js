@@ -1443,9 +1443,14 @@ class Engine {
 		const slots = await native().replayMap(this.ctx, batch);
 		return new MapReplay(batch, slots);
 	}
-	/** The sparse LWW path (fmt_map_*_sparse): any key pool size, live entries only. */
-	async replayMapSparse(batch) {
-		const r = await native().replayMapSparse(this.ctx, batch);
+	/**
+	 * The sparse LWW path (fmt_map_*_sparse): any key pool size, live entries only. By default a
+	 * document with more than 2048 distinct keys or 16384 ops rejects the batch with
+	 * FMT_E_CAPACITY; with {tiered: true} such documents replay in the HBM tier
+	 * (fmt_map_run_sparse_tiered), the local client's events (localOps) on top of it as usual.
+	 */
+	async replayMapSparse(batch, options = {}) {
+		const r = await native().replayMapSparse(this.ctx, batch, options.tiered === true);
 		return new SparseMapReplay(batch, r.counts, r.entries, r.pending);
 	}
 	close() {

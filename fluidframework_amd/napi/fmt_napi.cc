@@ -26,13 +26,15 @@
 //   fetchRmClientsHi(ctx, doc, nLeaves) -> BigUint64Array            fmt_mt_fetch_rm_clients_hi (ids 64..127)
 //   fetchRegen(ctx, doc) -> {ops: ArrayBuffer, text: Uint16Array}     fmt_mt_fetch_regen (f4 reconnects)
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
-//   replayMapSparse(ctx, batch) -> Promise<{counts, entries}>        fmt_map_load_sparse + run + fetch
+//   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
+//                                                  (tiered: fmt_map_run_sparse_tiered, no per-document limits)
 //   summarizeLegacy(ctx, quotedKeys, values, chunk, threads) -> Promise<timing>   fmt_mt_summarize_legacy
 //   summaryBlobs(ctx, doc) -> {header, body?}                        fmt_mt_summary_blobs
 //   stats(ctx) -> {kernelMs, totalMs, ops, docs, bytesRead, bytesWritten, launches}
 //   sizes: {mtOp, mapOp, leaf, docResult, propset, mapSlot}          struct sizes for the JS views
 #include <node_api.h>
 
+#include <dlfcn.h>
 #include <execinfo.h>
 #include <unistd.h>
 
@@ -45,6 +47,7 @@
 #include <vector>
 
 #include "fmt.h"
+#include "fmt_map_tiered.h"
 
 namespace {
 
@@ -396,6 +399,7 @@ struct Job {
   uint64_t map_n_ops = 0;
   const uint64_t* map_offs = nullptr;
   uint32_t n_docs = 0, key_bound = 0;
+  bool tiered = false;       // sparse map: fmt_map_run_sparse_tiered
   std::vector<uint8_t> out;  // headers, map slots, sparse counts
   std::vector<uint8_t> out2; // sparse entries
   // sparse map with the local client's events (fmt_map_pending_*): events, offsets, results
@@ -423,7 +427,26 @@ void Execute(napi_env, void* p) {  // libuv worker thread: no N-API calls here
     }
   } else if (j->kind == Job::kMapSparse) {
     j->rc = fmt_map_load_sparse(ctx, j->map_ops, j->map_n_ops, j->map_offs, j->n_docs, j->key_bound);
-    if (j->rc == FMT_OK) j->rc = fmt_map_run_sparse(ctx);
+    if (j->rc == FMT_OK && j->tiered) {
+      // fmt_map_tiered.h, looked up in the loaded libfmt at the call: the addon itself needs only fmt.h's
+      // entry points, and a libfmt without the HBM tier refuses the request instead of failing to load
+      // (node loads addons RTLD_LOCAL, so the library is found through one of its own symbols)
+      using TieredFn = decltype(&fmt_map_run_sparse_tiered);
+      TieredFn tiered = nullptr;
+      Dl_info where{};
+      if (dladdr(reinterpret_cast<void*>(&fmt_map_run_sparse), &where) != 0 && where.dli_fname != nullptr) {
+        if (void* lib = dlopen(where.dli_fname, RTLD_LAZY | RTLD_NOLOAD))  // (kept: libfmt stays loaded anyway)
+          tiered = reinterpret_cast<TieredFn>(dlsym(lib, "fmt_map_run_sparse_tiered"));
+      }
+      if (tiered != nullptr) {
+        j->rc = tiered(ctx);
+      } else {
+        j->rc = FMT_E_UNSUPPORTED;
+        j->err = "replayMapSparse: this libfmt has no fmt_map_run_sparse_tiered";
+      }
+    } else if (j->rc == FMT_OK) {
+      j->rc = fmt_map_run_sparse(ctx);
+    }
     uint64_t n = 0;
     j->out.resize(size_t(j->n_docs) * sizeof(uint32_t));
     if (j->rc == FMT_OK)  // sizes first (counts + total), then the packed entries
@@ -460,7 +483,7 @@ void Execute(napi_env, void* p) {  // libuv worker thread: no N-API calls here
       j->rc = fmt_mt_fetch_headers(ctx, reinterpret_cast<fmt_mt_doc_result*>(j->out.data()));
     }
   }
-  if (j->rc != FMT_OK) j->err = fmt_last_error(ctx);
+  if (j->rc != FMT_OK && j->err.empty()) j->err = fmt_last_error(ctx);
 }
 
 void Complete(napi_env env, napi_status, void* p) {  // JS thread
@@ -708,14 +731,15 @@ napi_value ReplayMap(napi_env env, napi_callback_info info) {
   return queue(env, j, argv[0], "fmtReplayMap");
 }
 
-// replayMapSparse(ctx, {ops, docOpOffsets, keyBound, localOps?, localOffsets?}) -> Promise<{counts,
-// entries, pending?}>: the sparse LWW path (key pools of any size): counts = n_docs u32 live-entry
+// replayMapSparse(ctx, {ops, docOpOffsets, keyBound, localOps?, localOffsets?}, tiered = false) ->
+// Promise<{counts, entries, pending?}>: the sparse LWW path (key pools of any size): counts = n_docs u32 live-entry
 // counts, entries = fmt_map_entry records of all documents packed in document order, each
 // document's in JS Map insertion order; with the local client's events, pending = {counts, status,
-// entries} of the optimistic view (fmt_map_pending_run / fetch).
+// entries} of the optimistic view (fmt_map_pending_run / fetch). tiered: documents past the LDS tier's
+// limits replay in the HBM tier (fmt_map_run_sparse_tiered) instead of rejecting with FMT_E_CAPACITY.
 napi_value ReplayMapSparse(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
+  size_t argc = 3;
+  napi_value argv[3];
   CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   Ctx* c;
   if (argc < 2 || !get_ctx(env, argv[0], &c)) return nullptr;
@@ -737,6 +761,7 @@ napi_value ReplayMapSparse(napi_env env, napi_callback_info info) {
   auto* j = new Job;
   j->c = c;
   j->kind = Job::kMapSparse;
+  if (argc >= 3 && napi_get_value_bool(env, argv[2], &j->tiered) != napi_ok) j->tiered = false;
   j->map_ops = static_cast<const fmt_map_op*>(ops);
   j->map_n_ops = n_ops_b / sizeof(fmt_map_op);
   j->map_offs = static_cast<const uint64_t*>(offs);

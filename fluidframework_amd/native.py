@@ -253,6 +253,7 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_fetch_rm_clients_hi", [P, U32, P, U32]),
                            ("fmt_mt_fetch_rm_clients_hi2", [P, U32, P, U32]),
                            ("fmt_map_pending_run", [P, P, U64, P]),
+                           ("fmt_map_run_sparse_tiered", [P]),
                            ("fmt_mt_fetch_regen", [P, U32, P, U32, P, U32, ctypes.POINTER(U32), ctypes.POINTER(U32)]),
                            ("fmt_map_pending_fetch", [P, P, P, P, U64, ctypes.POINTER(U64)]),
                            ("fmt_mt_summarize_v1", [P, P, U32, P, U32, P, P, U32, U32, ctypes.POINTER(FmtSummaryTiming)]),
@@ -280,6 +281,8 @@ EXPORTED_SYMBOLS = [
 
 # include/fmt_v1.h (bulk SnapshotV1 summaries)
 EXPORTED_SYMBOLS_V1 = ["fmt_mt_summarize_v1", "fmt_mt_summary_v1_blobs", "fmt_mt_summary_v1_body"]
+# include/fmt_map_tiered.h (the sparse map path with its HBM tier)
+EXPORTED_SYMBOLS_MAP_TIERED = ["fmt_map_run_sparse_tiered"]
 
 
 def _c_strings(strs):
@@ -381,6 +384,48 @@ def mt_plan(batch, struct=None) -> MtPlanResult:
     return r
 
 
+class MapLargePlanResult:
+    """What map_large_plan read back (csrc/map_plan.h MapLargePlan): `status`, `message` (None: FMT_OK),
+    `tile`, `scratch_bytes`, `slots`, `ops`, `regions` (name -> first 32-bit word: key, first, del, last,
+    value, op_slot, tile_count, clear), `docs` (one row per overflowing document: doc, n_ops, slots,
+    table_off, op_slot_off, first_tile, n_tiles, shift), `tile_doc` (index into docs) and `tile_first`."""
+
+
+MAP_LARGE_REGIONS = ("key", "first", "del", "last", "value", "op_slot", "tile_count", "clear")
+MAP_LARGE_DOC_FIELDS = ("doc", "n_ops", "slots", "table_off", "op_slot_off", "first_tile", "n_tiles", "shift")
+
+
+def map_large_plan(op_counts, overflow_docs) -> MapLargePlanResult:
+    """fmt_internal_map_large_plan: the host half of the sparse map path's HBM tier over a batch of
+    documents with `op_counts` ops each, of which `overflow_docs` (ascending) overflowed the LDS tier.
+    No device needed."""
+    offs = np.zeros(len(op_counts) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(np.asarray(op_counts, dtype=np.uint64))
+    ovf = np.ascontiguousarray(overflow_docs, dtype=np.uint32)
+    P = ctypes.c_void_p
+    f = lib().fmt_internal_map_large_plan
+    f.argtypes = [P, ctypes.c_uint32, P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(P),
+                  ctypes.POINTER(ctypes.c_uint64)]
+    err, out, n = ctypes.c_char_p(), P(), ctypes.c_uint64()
+    r = MapLargePlanResult()
+    r.status = f(_ptr(offs), len(op_counts), _ptr(ovf) if len(ovf) else None, len(ovf), ctypes.byref(err),
+                 ctypes.byref(out), ctypes.byref(n))
+    r.message = err.value.decode() if err.value else None
+    w = np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy()
+    r.tile, r.scratch_bytes, r.slots, r.ops = (int(x) for x in w[:4])
+    r.regions = {name: int(x) for name, x in zip(MAP_LARGE_REGIONS, w[4:12])}
+    at = 12
+    got = []
+    for width in (len(MAP_LARGE_DOC_FIELDS), 1, 1):
+        cnt = int(w[at]) * width
+        got.append(w[at + 1 : at + 1 + cnt])
+        at += 1 + cnt
+    assert at == len(w)
+    r.docs = got[0].reshape(-1, len(MAP_LARGE_DOC_FIELDS))
+    r.tile_doc, r.tile_first = got[1], got[2]
+    return r
+
+
 def capacity():
     a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
     lib().fmt_mt_capacity(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
@@ -464,6 +509,10 @@ class Engine:
 
     def map_run_sparse(self):
         self._check(self.L.fmt_map_run_sparse(self.h))
+
+    def map_run_sparse_tiered(self):
+        """fmt_map_run_sparse_tiered: the LDS tier, then the HBM tier for the documents it refused."""
+        self._check(self.L.fmt_map_run_sparse_tiered(self.h))
 
     def map_fetch_sparse(self):
         """(counts[n_docs], entries[sum(counts)]) with MAP_ENTRY_DTYPE, documents in order."""

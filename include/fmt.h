@@ -483,14 +483,19 @@ int fmt_map_check(fmt_ctx* ctx);
 
 /* Sparse LWW for key pools of any size (key_bound up to 2^32 - 1): the per-key reductions run in
  * a per-document LDS hash table and the result is one entry per LIVE key, in JS Map insertion order
- * (birth seq ascending; map.ts:176-246 orders array-index keys first on top of that). Limits per
- * document: FMT_MAP_SPARSE_MAX_KEYS distinct keys and FMT_MAP_SPARSE_MAX_OPS ops (beyond them the
- * document gets no entries and fmt_map_fetch_sparse returns FMT_E_CAPACITY). */
+ * (birth seq ascending; map.ts:176-246 orders array-index keys first on top of that). The LDS
+ * tier (fmt_map_run_sparse) has limits per document: FMT_MAP_SPARSE_MAX_KEYS distinct keys after the
+ * last clear and FMT_MAP_SPARSE_MAX_OPS ops (beyond them the document gets no entries and
+ * fmt_map_fetch_sparse returns FMT_E_CAPACITY). fmt_map_run_sparse_tiered (fmt_map_tiered.h) has
+ * none: it replays such documents with their tables in HBM. */
 typedef struct fmt_map_entry {
   uint32_t key;
   uint32_t value;      /* value id (FMT_MAP_VALUE_UNDEFINED: set with value undefined) */
   uint32_t birth_seq;  /* seq of the first set after the key's last delete/clear */
 } fmt_map_entry;
+/* The LDS tier's limits (fmt_map_run_sparse). The tiered run is bounded only by device memory
+ * (under 84.02 B of tables per op of an overflowing document) and 32-bit ordinals (a document of
+ * fewer than 2^30 ops). */
 #define FMT_MAP_SPARSE_MAX_KEYS 2048
 #define FMT_MAP_SPARSE_MAX_OPS 16384
 /* Stage a batch for the sparse path (no dense per-(doc, key) output is allocated). */
@@ -498,6 +503,8 @@ int fmt_map_load_sparse(fmt_ctx* ctx, const fmt_map_op* ops, uint64_t n_ops,
                         const uint64_t* doc_op_offsets, uint32_t n_docs, uint32_t key_bound);
 /* Replay it (asynchronous on the ctx stream). */
 int fmt_map_run_sparse(fmt_ctx* ctx);
+/* fmt_map_run_sparse_tiered (fmt_map_tiered.h) is the same run followed by an HBM tier for the
+ * documents this one refuses. */
 /* counts[d] = live entries of document d (n_docs entries); entries of all documents packed in
  * document order into `entries` (cap_entries; *n_entries = their total). Synchronizes. */
 int fmt_map_fetch_sparse(fmt_ctx* ctx, uint32_t* counts, fmt_map_entry* entries, uint64_t cap_entries,
@@ -528,9 +535,10 @@ typedef struct fmt_map_local_op {
  * findLast and the iterator's scans are linear in the pending list), so a longer event list gets
  * status FMT_E_CAPACITY and no entries instead of stalling the launch. */
 #define FMT_MAP_PENDING_MAX_EVENTS 16384
-/* Every document's optimistic view over the sequenced entries of the last fmt_map_run_sparse and
- * the documents' local events (document d's at events[doc_event_offsets[d] .. [d + 1])), one
- * device thread per document. Asynchronous on the ctx stream. */
+/* Every document's optimistic view over the sequenced entries of the last fmt_map_run_sparse (or
+ * fmt_map_run_sparse_tiered) and the documents' local events (document d's at
+ * events[doc_event_offsets[d] .. [d + 1])), one device thread per document. Asynchronous on the
+ * ctx stream. */
 int fmt_map_pending_run(fmt_ctx* ctx, const fmt_map_local_op* events, uint64_t n_events,
                         const uint64_t* doc_event_offsets);
 /* counts[d] = optimistic entries of document d; entries packed in document order, each document's

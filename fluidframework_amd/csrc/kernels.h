@@ -44,6 +44,25 @@ hipError_t launchMapPending(const fmt_map_local_op* events, const uint64_t* evOf
                             const uint64_t* seqOffs, const uint32_t* seqCounts, uint32_t nDocs, void* scratch,
                             const uint64_t* outBase, fmt_map_entry* out, uint32_t* outCounts, int32_t* outStatus,
                             hipStream_t stream);
+// ---- bulk SharedMap summaries of the sparse path (map_summary.hip; the host half: map_sum_plan.h)
+struct MapSummaryArgs {
+  const fmt_map_entry* entries;  // the replay's entries (birth order) at offsets[d], counts[d] each: only read
+  const uint64_t* offsets;
+  const uint32_t* counts;
+  const uint32_t* keyRank;       // per key id: its array-index value, or 0xFFFFFFFF
+  const uint32_t* valUnits;      // per value id: UTF-16 units of its JSON text
+  fmt_map_entry* ordered;        // out, same layout: the entries in summary order
+  uint32_t* tags;                // out, same layout: the blob each ordered entry lands in, 0xFFFFFFFF: the header
+  uint32_t* nBlobs;              // out, per document
+  uint32_t* list;                // nDocs + 1 words, [0] zeroed by the caller: the documents of more than 64 entries
+  uint32_t nDocs, nKeys, nValues;
+};
+// Documents of more than 2048 live entries are copied unordered (tags 0xFFFFFFFF, nBlobs 0).
+hipError_t launchMapSummary(const MapSummaryArgs& a, int numCUs, hipStream_t stream);
+// packed (32-bit words; N = packedOff[nDocs]): [0, 3N) entries, [3N, 4N) tags, [4N, 4N + nDocs) blob counts
+hipError_t launchMapSummaryPack(const fmt_map_entry* ordered, const uint32_t* tags, const uint32_t* nBlobs,
+                                const uint64_t* offsets, const uint32_t* counts, const uint64_t* packedOff, uint32_t nDocs,
+                                uint32_t* packed, hipStream_t stream);
 hipError_t launchMapLww(const fmt_map_op* ops, const uint64_t* offsets, uint32_t nDocs, uint32_t keyBound,
                         fmt_map_slot* out, int* error, int numCUs, hipStream_t stream, uint32_t* scratch);
 

@@ -15,12 +15,14 @@
 #include <vector>
 
 #include "../../include/fmt.h"
+#include "../../include/fmt_map_summary.h"
 #include "../../include/fmt_map_tiered.h"
 #include "../../include/fmt_v1.h"
 #include "huge_engine.h"
 #include "jsnum.h"
 #include "mt_engine.h"  // fmt_mt::AdjustTables
 #include "mt_plan.h"
+#include "map_sum_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -144,6 +146,18 @@ struct fmt_ctx {
   DevBuf<uint32_t> mapPendCounts;
   DevBuf<int32_t> mapPendStatus;
   bool mapPendRan = false;
+  // bulk summaries of the sparse path (fmt_map_summarize, map_summary.hip): the tiered run completed
+  // (no document is left refused), the ordered entries and tags in the entries' layout, per-document
+  // blob counts, the list of documents past one wave, the tables, the packed host copy, the blobs
+  bool mapTieredDone = false;
+  bool mapSumHostOnly = false;  // fmt_internal_map_summary_host_only: every document ordered on the host
+  DevBuf<fmt_map_entry> mapSumEntries;
+  DevBuf<uint32_t> mapSumTags, mapSumNBlobs, mapSumList, mapSumKeyRank, mapSumValUnits, mapSumPacked;
+  PinnedBuf<uint32_t> mapSumHost;
+  fmt_plan::MapSumBlobs mapSumBlobs;
+  std::vector<int32_t> mapSumStatus;
+  bool mapSumDone = false;
+  uint64_t mapSumN = 0;  // live entries of the last summary
 
   // merge-tree
   DevBuf<fmt_mt_op> mtOps;
@@ -418,6 +432,9 @@ void fmt_close(fmt_ctx* c) {
   c->mapLgScratch.release();
   c->mapLgDocs.release();
   c->mapPackedOff.release();
+  c->mapSumEntries.release();
+  for (auto* q : {&c->mapSumTags, &c->mapSumNBlobs, &c->mapSumList, &c->mapSumKeyRank, &c->mapSumValUnits, &c->mapSumPacked})
+    q->release();
   c->errWord.release();
   c->mtOps.release();
   c->mtOffs.release();
@@ -561,6 +578,9 @@ static int mapStage(fmt_ctx* c, const fmt_map_op* ops, uint64_t nOps, const uint
   c->mapSparse = sparse;
   c->mapSparseRan = false;
   c->mapPendRan = false;
+  c->mapTieredDone = false;
+  c->mapSumDone = false;  // (a summary's blobs are valid until the next map load)
+  c->mapSumBlobs = fmt_plan::MapSumBlobs{};
   c->mapOffsHost.assign(offs, offs + nDocs + 1ull);
   return FMT_OK;
 }
@@ -595,6 +615,7 @@ int fmt_map_run_sparse(fmt_ctx* c) {
   c->stats.launches = 1;
   c->mapSparseRan = true;
   c->mapPendRan = false;
+  c->mapTieredDone = false;
   return FMT_OK;
 }
 
@@ -620,9 +641,11 @@ int fmt_map_run_sparse_tiered(fmt_ctx* c) {
   c->stats.launches = 1;
   c->mapSparseRan = true;  // (the LDS tier's documents are valid whatever becomes of the rest)
   c->mapPendRan = false;
+  c->mapTieredDone = false;
   uint32_t nOvf = 0;
   FMT_HIP(c, hipMemcpyAsync(&nOvf, c->mapOvf.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   FMT_HIP(c, hipStreamSynchronize(c->stream));
+  c->mapTieredDone = nOvf == 0;
   if (nOvf == 0) return FMT_OK;
   std::vector<uint32_t> ovf(nOvf);
   FMT_HIP(c, hipMemcpy(ovf.data(), c->mapOvf.p + 1, nOvf * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -668,6 +691,7 @@ int fmt_map_run_sparse_tiered(fmt_ctx* c) {
   c->stats.bytes_read += P.ops * (2 * sizeof(fmt_map_op) + 3 * 4) + nTiles * (2 * 8 + 2 * 4);
   c->stats.bytes_written += P.slots * 20 + P.ops * 4 + nTiles * 8 + nOvf * 4ull;
   c->stats.launches += launches;
+  c->mapTieredDone = true;
   return FMT_OK;
 }
 
@@ -774,6 +798,161 @@ int fmt_map_pending_fetch(fmt_ctx* c, uint32_t* counts, int32_t* status, fmt_map
     FMT_HIP(c, hipStreamSynchronize(c->stream));
   }
   return FMT_OK;
+}
+
+// Bulk SharedMap summaries of the last sparse run (include/fmt_map_summary.h): the tables on the host
+// threads, ordering and blob assignment on the device (map_summary.hip; documents past its tier and
+// the host-only switch: map_sum_plan.h), one packed copy back, the JSON on the host threads.
+int fmt_map_summarize(fmt_ctx* c, const char* const* keys, uint32_t nKeys, const char* const* values, uint32_t nValues,
+                      uint32_t threads, fmt_map_summary_timing* timing) {
+  if (c == nullptr || (nKeys && keys == nullptr) || (nValues && values == nullptr))
+    return setErr(c, FMT_E_USAGE, "fmt_map_summarize: null arguments");
+  if (!c->mapLoaded || !c->mapSparse || !c->mapSparseRan)
+    return setErr(c, FMT_E_USAGE, "fmt_map_summarize needs a sparse map run (fmt_map_run_sparse or fmt_map_run_sparse_tiered) first");
+  using clk = std::chrono::steady_clock;
+  auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  FMT_HIP(c, hipSetDevice(c->device));
+  const uint32_t nd = c->mapDocs;
+  int errWord = 0;
+  std::vector<uint32_t> counts(nd);
+  FMT_HIP(c, hipMemcpyAsync(&errWord, c->errWord.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (nd) FMT_HIP(c, hipMemcpyAsync(counts.data(), c->mapCounts.p, nd * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  if (errWord & 1) return setErr(c, FMT_E_DATA, "an op referenced a key id >= key_bound");
+  if ((errWord & 2) && !c->mapTieredDone)
+    return setErr(c, FMT_E_CAPACITY,
+                  "a document exceeded the sparse path's keys or ops per document and has no entries: run "
+                  "fmt_map_run_sparse_tiered before fmt_map_summarize");
+  c->mapSumDone = false;
+  const uint32_t nt = threads ? threads : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  // host tables
+  const auto tA = clk::now();
+  fmt_plan::MapSumTables T;
+  fmt_plan::mapSumBuildTables(keys, nKeys, values, nValues, nt, T);
+  std::vector<uint64_t> at(nd + 1ull, 0);  // packed position of each document's first entry
+  for (uint32_t d = 0; d < nd; d++) at[d + 1] = at[d] + counts[d];
+  const uint64_t n = at[nd];
+  const auto tB = clk::now();
+  const bool device = !c->mapSumHostOnly;
+  const uint64_t words = device ? 4 * n + nd : 3 * n;
+  FMT_HIP(c, c->mapPackedOff.reserve(nd + 1ull));
+  FMT_HIP(c, c->mapSumPacked.reserve(words));
+  FMT_HIP(c, c->mapSumHost.reserve(4 * n + nd));
+  FMT_HIP(c, hipMemcpyAsync(c->mapPackedOff.p, at.data(), (nd + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  float kms = 0.f;
+  if (device) {
+    FMT_HIP(c, c->mapSumEntries.reserve(c->mapNOps));
+    FMT_HIP(c, c->mapSumTags.reserve(c->mapNOps));
+    FMT_HIP(c, c->mapSumNBlobs.reserve(nd));
+    FMT_HIP(c, c->mapSumList.reserve(nd + 1ull));
+    FMT_HIP(c, c->mapSumKeyRank.reserve(nKeys));
+    FMT_HIP(c, c->mapSumValUnits.reserve(nValues));
+    if (nKeys) FMT_HIP(c, hipMemcpyAsync(c->mapSumKeyRank.p, T.keyRank.data(), nKeys * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nValues)
+      FMT_HIP(c, hipMemcpyAsync(c->mapSumValUnits.p, T.valUnits.data(), nValues * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    FMT_HIP(c, hipMemsetAsync(c->mapSumList.p, 0, sizeof(uint32_t), c->stream));
+    fmt_kernels::MapSummaryArgs a{};
+    a.entries = c->mapEntries.p;
+    a.offsets = c->mapOffs.p;
+    a.counts = c->mapCounts.p;
+    a.keyRank = c->mapSumKeyRank.p;
+    a.valUnits = c->mapSumValUnits.p;
+    a.ordered = c->mapSumEntries.p;
+    a.tags = c->mapSumTags.p;
+    a.nBlobs = c->mapSumNBlobs.p;
+    a.list = c->mapSumList.p;
+    a.nDocs = nd;
+    a.nKeys = nKeys;
+    a.nValues = nValues;
+    FMT_HIP(c, hipEventRecord(c->evS0, c->stream));  // (own events, as the merge-tree summaries)
+    FMT_HIP(c, fmt_kernels::launchMapSummary(a, c->numCUs, c->stream));
+    FMT_HIP(c, hipEventRecord(c->evS1, c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+    FMT_HIP(c, hipEventElapsedTime(&kms, c->evS0, c->evS1));
+  }
+  // fetch: one pack, one copy
+  const auto t0 = clk::now();
+  if (device)
+    FMT_HIP(c, fmt_kernels::launchMapSummaryPack(c->mapSumEntries.p, c->mapSumTags.p, c->mapSumNBlobs.p, c->mapOffs.p,
+                                                 c->mapCounts.p, c->mapPackedOff.p, nd, c->mapSumPacked.p, c->stream));
+  else  // the replay's entries as they are
+    FMT_HIP(c, fmt_kernels::launchMapSparsePack(c->mapEntries.p, c->mapOffs.p, c->mapCounts.p, c->mapPackedOff.p, nd,
+                                                reinterpret_cast<fmt_map_entry*>(c->mapSumPacked.p), c->stream));
+  uint32_t* const host = c->mapSumHost.p;
+  if (words) FMT_HIP(c, hipMemcpyAsync(host, c->mapSumPacked.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  const auto t1 = clk::now();
+  fmt_map_entry* const ent = reinterpret_cast<fmt_map_entry*>(host);
+  uint32_t* const tags = host + 3 * n;
+  uint32_t* const nBlobs = host + 4 * n;
+  // documents past the device tier (their entries came back in birth order) are ordered here, from a
+  // copy the ordering reads while it writes the packed arrays in place
+  uint32_t hostDocs = 0;
+  {
+    auto past = [&](uint32_t d) { return !device || counts[d] > fmt_plan::kMapSumDeviceMax; };
+    std::vector<uint64_t> from(nd + 1ull, 0);
+    for (uint32_t d = 0; d < nd; d++) from[d + 1] = from[d] + (past(d) ? counts[d] : 0u);
+    std::vector<fmt_map_entry> birth(from[nd]);
+    for (uint32_t d = 0; d < nd; d++)
+      if (past(d) && counts[d]) std::memcpy(birth.data() + from[d], ent + at[d], counts[d] * sizeof(fmt_map_entry));
+    hostDocs = fmt_plan::mapSumOrderDocs(birth.data(), from.data(), ent, tags, nBlobs, counts.data(), at.data(), nd, T, nt, past);
+  }
+  c->mapSumStatus.assign(nd, FMT_OK);
+  fmt_plan::mapSumThreads(nt, [&](uint32_t t) {
+    const uint32_t per = (nd + nt - 1) / nt, lo = std::min(nd, per * t), hi = std::min(nd, lo + per);
+    for (uint32_t d = lo; d < hi; d++)
+      if (!fmt_plan::mapSumInTables(ent + at[d], counts[d], nKeys, nValues)) c->mapSumStatus[d] = FMT_E_USAGE;
+  });
+  fmt_plan::mapSumFormat(ent, tags, nBlobs, counts.data(), at.data(), c->mapSumStatus.data(), nd, keys, values, T, nt,
+                         c->mapSumBlobs);
+  const auto t2 = clk::now();
+  c->mapSumDone = true;
+  c->mapSumN = n;
+  c->timed = false;
+  c->timed2 = false;
+  c->stats = fmt_stats{};
+  c->stats.kernel_ms = kms;
+  c->stats.total_ms = kms;
+  c->stats.ops = n;
+  c->stats.docs = nd;
+  // entries, their key ranks and value units, counts and offsets in; ordered entries, tags, blob counts out
+  c->stats.bytes_read = device ? n * (sizeof(fmt_map_entry) + 8) + nd * 12ull : 0;
+  c->stats.bytes_written = device ? n * (sizeof(fmt_map_entry) + 4) + nd * 4ull : 0;
+  c->stats.launches = device ? 3 : 1;
+  if (timing) {
+    timing->kernel_ms = kms;
+    timing->fetch_ms = ms(t0, t1);
+    timing->format_ms = ms(tA, tB) + ms(t1, t2);
+    timing->bytes = c->mapSumBlobs.bytes;
+    timing->threads = nt;
+    timing->host_ordered_docs = hostDocs;
+  }
+  return FMT_OK;
+}
+
+static int mapSummaryPiece(fmt_ctx* c, uint32_t doc, uint32_t piece, const char** out, size_t* len, uint32_t* nBlobs,
+                           const char* what) {
+  if (c == nullptr || !c->mapSumDone || doc >= c->mapSumStatus.size())
+    return setErr(c, FMT_E_USAGE, std::string(what) + ": no summary for doc (fmt_map_summarize first)");
+  if (c->mapSumStatus[doc] != FMT_OK)
+    return setErr(c, c->mapSumStatus[doc], "a live entry's key or value id is outside the tables passed to fmt_map_summarize");
+  const fmt_plan::MapSumBlobs& B = c->mapSumBlobs;
+  const uint64_t first = B.pieceAt[doc], pieces = B.pieceAt[doc + 1] - first;
+  if (piece >= pieces) return setErr(c, FMT_E_USAGE, std::string(what) + ": no such blob");
+  const uint64_t b = piece ? B.ends[first + piece - 1] : 0, e = B.ends[first + piece];
+  if (out) *out = B.buf[B.docThread[doc]].data() + B.docAt[doc] + b;
+  if (len) *len = e - b;
+  if (nBlobs) *nBlobs = static_cast<uint32_t>(pieces - 1);
+  return FMT_OK;
+}
+
+int fmt_map_summary_blobs(fmt_ctx* c, uint32_t doc, const char** header, size_t* headerLen, uint32_t* nBlobs) {
+  return mapSummaryPiece(c, doc, 0, header, headerLen, nBlobs, "fmt_map_summary_blobs");
+}
+
+int fmt_map_summary_blob(fmt_ctx* c, uint32_t doc, uint32_t k, const char** blob, size_t* blobLen) {
+  if (k == 0xFFFFFFFFu) return setErr(c, FMT_E_USAGE, "fmt_map_summary_blob: no such blob");
+  return mapSummaryPiece(c, doc, k + 1, blob, blobLen, nullptr, "fmt_map_summary_blob");
 }
 
 static int runMap(fmt_ctx* c, const fmt_map_op* ops, const uint64_t* offs, uint32_t nDocs, uint32_t keyBound,
@@ -2429,6 +2608,71 @@ int fmt_internal_legacy_format(const void* runs, uint32_t nRuns, const uint16_t*
   *ends = blobEnds.data();
   *nBlobs = static_cast<uint32_t>(blobEnds.size());
   return rc;
+}
+
+// Test hook (not part of fmt_map_summary.h): fmt_map_summarize's host half (map_sum_plan.h) over fetched
+// sparse entries (fmt_map_fetch_sparse's counts and packed birth-ordered entries), no device needed:
+// tables, ordering, blob scan and formatter on `threads` host threads (0: 1). ordered / tags (the live
+// entries each), n_blobs / status (n_docs each) may be NULL. *docs: per document where its header
+// starts, its blobs following; *piece_at (n_docs + 1) and *ends as MapSumBlobs. A document with status
+// FMT_E_USAGE has no pieces. All valid until the calling thread's next call.
+int fmt_internal_map_summary_format(const uint32_t* counts, const fmt_map_entry* entries, uint32_t nDocs,
+                                    const char* const* keys, uint32_t nKeys, const char* const* values, uint32_t nValues,
+                                    uint32_t threads, fmt_map_entry* ordered, uint32_t* tags, uint32_t* nBlobs, int32_t* status,
+                                    const char* const** docs, const uint64_t** pieceAt, const uint64_t** ends) {
+  static thread_local fmt_plan::MapSumBlobs B;
+  static thread_local std::vector<const char*> docPtr;
+  if ((nDocs && counts == nullptr) || (nKeys && keys == nullptr) || (nValues && values == nullptr) || docs == nullptr ||
+      pieceAt == nullptr || ends == nullptr)
+    return FMT_E_USAGE;
+  const uint32_t nt = threads ? threads : 1u;
+  std::vector<uint64_t> at(nDocs + 1ull, 0);
+  for (uint32_t d = 0; d < nDocs; d++) at[d + 1] = at[d] + counts[d];
+  const uint64_t n = at[nDocs];
+  if (n && entries == nullptr) return FMT_E_USAGE;
+  fmt_plan::MapSumTables T;
+  fmt_plan::mapSumBuildTables(keys, nKeys, values, nValues, nt, T);
+  std::vector<fmt_map_entry> ord(n);
+  std::vector<uint32_t> tg(n), nb(nDocs);
+  std::vector<int32_t> st(nDocs, FMT_OK);
+  fmt_plan::mapSumOrderDocs(entries, at.data(), ord.data(), tg.data(), nb.data(), counts, at.data(), nDocs, T, nt,
+                            [](uint32_t) { return true; });
+  for (uint32_t d = 0; d < nDocs; d++)
+    if (!fmt_plan::mapSumInTables(ord.data() + at[d], counts[d], nKeys, nValues)) st[d] = FMT_E_USAGE;
+  fmt_plan::mapSumFormat(ord.data(), tg.data(), nb.data(), counts, at.data(), st.data(), nDocs, keys, values, T, nt, B);
+  docPtr.assign(nDocs, nullptr);
+  for (uint32_t d = 0; d < nDocs; d++) docPtr[d] = B.buf[B.docThread[d]].data() + B.docAt[d];
+  if (ordered && n) std::memcpy(ordered, ord.data(), n * sizeof(fmt_map_entry));
+  if (tags && n) std::memcpy(tags, tg.data(), n * sizeof(uint32_t));
+  if (nBlobs && nDocs) std::memcpy(nBlobs, nb.data(), nDocs * sizeof(uint32_t));
+  if (status && nDocs) std::memcpy(status, st.data(), nDocs * sizeof(int32_t));
+  *docs = docPtr.data();
+  *pieceAt = B.pieceAt.data();
+  *ends = B.ends.data();
+  return FMT_OK;
+}
+
+// Test hook: the ordered entries, tags (the live entries each) and blob counts (n_docs) of the last
+// fmt_map_summarize as they came back from the device (documents past the device tier: as the host
+// ordered them), packed in document order.
+int fmt_internal_map_summary_arrays(fmt_ctx* c, fmt_map_entry* ordered, uint32_t* tags, uint32_t* nBlobs, uint64_t cap) {
+  if (c == nullptr || !c->mapSumDone) return setErr(c, FMT_E_USAGE, "fmt_internal_map_summary_arrays before fmt_map_summarize");
+  const uint32_t nd = c->mapDocs;
+  const uint64_t n = c->mapSumN;
+  if (cap < n) return setErr(c, FMT_E_USAGE, "fmt_internal_map_summary_arrays: cap below the live entries");
+  const uint32_t* host = c->mapSumHost.p;
+  if (ordered && n) std::memcpy(ordered, host, n * sizeof(fmt_map_entry));
+  if (tags && n) std::memcpy(tags, host + 3 * n, n * sizeof(uint32_t));
+  if (nBlobs && nd) std::memcpy(nBlobs, host + 4 * n, nd * sizeof(uint32_t));
+  return FMT_OK;
+}
+
+// Measurement switch (tools/bench_map_summary.py only): on != 0 makes fmt_map_summarize skip the device
+// tier and order every document with map_sum_plan.h on its host threads.
+int fmt_internal_map_summary_host_only(fmt_ctx* c, int on) {
+  if (c == nullptr) return FMT_E_USAGE;
+  c->mapSumHostOnly = on != 0;
+  return FMT_OK;
 }
 
 // Internal diagnostic (not part of fmt.h): per-phase cycle totals of a FMT_PROFILE=1 build.

@@ -1364,8 +1364,9 @@ class MapReplay {
 /** Converged SharedMap state from the sparse path (key pools of any size): live entries per
  * document in JS Map insertion order (fmt_map_entry records). */
 class SparseMapReplay {
-	constructor(batch, counts, entries, pending) {
+	constructor(batch, counts, entries, pending, engine) {
 		this.batch = batch;
+		this.engine = engine;  // (for summarizeAll / summaryOf)
 		this.counts = new Uint32Array(counts);
 		this.view = new DataView(entries);
 		this.first = new Float64Array(this.counts.length + 1);
@@ -1418,6 +1419,22 @@ class SparseMapReplay {
 		return summary.mapSummary(this.rawEntries(doc).map(([k, v]) => [this.batch.keys[k],
 			v === MAP_VALUE_UNDEFINED ? undefined : this.batch.values[v]]));
 	}
+	/**
+	 * The summaries of every document at once (fmt_map_summarize: JS object order and blob split on the
+	 * device, JSON on host threads), from the sequenced entries: pending local state is not part of
+	 * a summary. Resolves to the timing; read each document's blobs with summaryOf(doc). Rejects with
+	 * FMT_E_UNSUPPORTED when the loaded libfmt lacks the call, and with FMT_E_CAPACITY after a replay
+	 * without {tiered: true} that refused a document.
+	 */
+	async summarizeAll(options) {
+		const o = options || {};
+		return native().summarizeMap(this.engine.ctx, this.batch.keys.map((k) => JSON.stringify(k)), this.batch.values,
+			o.threads || 0);
+	}
+	/** {header, blobs} of document doc from the last summarizeAll (throws with its status); what summarize(doc) builds. */
+	summaryOf(doc) {
+		return native().mapSummaryBlobs(this.engine.ctx, doc);
+	}
 	get(doc, key) {
 		const e = this.rawEntries(doc).find(([k]) => this.batch.keys[k] === key);
 		return e === undefined || e[1] === MAP_VALUE_UNDEFINED ? undefined : JSON.parse(this.batch.values[e[1]]);
@@ -1451,7 +1468,7 @@ class Engine {
 	 */
 	async replayMapSparse(batch, options = {}) {
 		const r = await native().replayMapSparse(this.ctx, batch, options.tiered === true);
-		return new SparseMapReplay(batch, r.counts, r.entries, r.pending);
+		return new SparseMapReplay(batch, r.counts, r.entries, r.pending, this);
 	}
 	close() {
 		native().close(this.ctx);

@@ -28,6 +28,8 @@
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
 //   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
 //                                                  (tiered: fmt_map_run_sparse_tiered, no per-document limits)
+//   summarizeMap(ctx, quotedKeys, values, threads) -> Promise<timing>   fmt_map_summarize (fmt_map_summary.h)
+//   mapSummaryBlobs(ctx, doc) -> {header, blobs}                        fmt_map_summary_blobs / _blob
 //   summarizeLegacy(ctx, quotedKeys, values, chunk, threads) -> Promise<timing>   fmt_mt_summarize_legacy
 //   summaryBlobs(ctx, doc) -> {header, body?}                        fmt_mt_summary_blobs
 //   stats(ctx) -> {kernelMs, totalMs, ops, docs, bytesRead, bytesWritten, launches}
@@ -47,6 +49,7 @@
 #include <vector>
 
 #include "fmt.h"
+#include "fmt_map_summary.h"
 #include "fmt_map_tiered.h"
 
 namespace {
@@ -393,7 +396,7 @@ struct Job {
   napi_deferred deferred = nullptr;
   Ctx* c = nullptr;
   std::vector<napi_ref> keep;  // input arrays stay alive (and unmoved) until Complete
-  enum Kind { kMergeTree, kMap, kMapSparse, kSummarize } kind = kMergeTree;
+  enum Kind { kMergeTree, kMap, kMapSparse, kSummarize, kSummarizeMap } kind = kMergeTree;
   fmt_mt_batch mt;
   const fmt_map_op* map_ops = nullptr;
   uint64_t map_n_ops = 0;
@@ -411,9 +414,21 @@ struct Job {
   std::vector<std::string> keys, values;
   uint32_t chunk = 0, threads = 0;
   fmt_summary_timing timing{};
+  fmt_map_summary_timing map_timing{};  // summarizeMap
   int rc = FMT_OK;
   std::string err;
 };
+
+// An entry point of fmt_map_tiered.h / fmt_map_summary.h, looked up in the loaded libfmt at the call:
+// the addon itself needs only fmt.h's entry points, and a libfmt without the symbol refuses the request
+// instead of failing to load (node loads addons RTLD_LOCAL, so the library is found through one of its
+// own symbols).
+void* libfmt_symbol(const char* name) {
+  Dl_info where{};
+  if (dladdr(reinterpret_cast<void*>(&fmt_map_run_sparse), &where) == 0 || where.dli_fname == nullptr) return nullptr;
+  void* lib = dlopen(where.dli_fname, RTLD_LAZY | RTLD_NOLOAD);  // (kept: libfmt stays loaded anyway)
+  return lib != nullptr ? dlsym(lib, name) : nullptr;
+}
 
 void Execute(napi_env, void* p) {  // libuv worker thread: no N-API calls here
   auto* j = static_cast<Job*>(p);
@@ -428,16 +443,8 @@ void Execute(napi_env, void* p) {  // libuv worker thread: no N-API calls here
   } else if (j->kind == Job::kMapSparse) {
     j->rc = fmt_map_load_sparse(ctx, j->map_ops, j->map_n_ops, j->map_offs, j->n_docs, j->key_bound);
     if (j->rc == FMT_OK && j->tiered) {
-      // fmt_map_tiered.h, looked up in the loaded libfmt at the call: the addon itself needs only fmt.h's
-      // entry points, and a libfmt without the HBM tier refuses the request instead of failing to load
-      // (node loads addons RTLD_LOCAL, so the library is found through one of its own symbols)
       using TieredFn = decltype(&fmt_map_run_sparse_tiered);
-      TieredFn tiered = nullptr;
-      Dl_info where{};
-      if (dladdr(reinterpret_cast<void*>(&fmt_map_run_sparse), &where) != 0 && where.dli_fname != nullptr) {
-        if (void* lib = dlopen(where.dli_fname, RTLD_LAZY | RTLD_NOLOAD))  // (kept: libfmt stays loaded anyway)
-          tiered = reinterpret_cast<TieredFn>(dlsym(lib, "fmt_map_run_sparse_tiered"));
-      }
+      const TieredFn tiered = reinterpret_cast<TieredFn>(libfmt_symbol("fmt_map_run_sparse_tiered"));
       if (tiered != nullptr) {
         j->rc = tiered(ctx);
       } else {
@@ -468,6 +475,18 @@ void Execute(napi_env, void* p) {  // libuv worker thread: no N-API calls here
         j->pentries.resize(size_t(np) * sizeof(fmt_map_entry));
         j->rc = fmt_map_pending_fetch(ctx, pc, ps, reinterpret_cast<fmt_map_entry*>(j->pentries.data()), np, &np);
       }
+    }
+  } else if (j->kind == Job::kSummarizeMap) {
+    using SummarizeFn = decltype(&fmt_map_summarize);
+    const SummarizeFn summarize = reinterpret_cast<SummarizeFn>(libfmt_symbol("fmt_map_summarize"));
+    std::vector<const char*> k, v;
+    for (const auto& x : j->keys) k.push_back(x.c_str());
+    for (const auto& x : j->values) v.push_back(x.c_str());
+    if (summarize != nullptr) {
+      j->rc = summarize(ctx, k.data(), uint32_t(k.size()), v.data(), uint32_t(v.size()), j->threads, &j->map_timing);
+    } else {
+      j->rc = FMT_E_UNSUPPORTED;
+      j->err = "summarizeMap: this libfmt has no fmt_map_summarize";
     }
   } else if (j->kind == Job::kSummarize) {
     std::vector<const char*> k, v;
@@ -511,6 +530,20 @@ void Complete(napi_env env, napi_status, void* p) {  // JS thread
       napi_set_named_property(env, p, "entries", buffer(j->pentries));
       napi_set_named_property(env, o, "pending", p);
     }
+    napi_resolve_deferred(env, j->deferred, o);
+  } else if (j->kind == Job::kSummarizeMap) {
+    napi_value o, v;
+    napi_create_object(env, &o);
+    auto num = [&](const char* k, double x) {
+      napi_create_double(env, x, &v);
+      napi_set_named_property(env, o, k, v);
+    };
+    num("kernelMs", j->map_timing.kernel_ms);
+    num("fetchMs", j->map_timing.fetch_ms);
+    num("formatMs", j->map_timing.format_ms);
+    num("bytes", double(j->map_timing.bytes));
+    num("threads", double(j->map_timing.threads));
+    num("hostOrderedDocs", double(j->map_timing.host_ordered_docs));
     napi_resolve_deferred(env, j->deferred, o);
   } else if (j->kind == Job::kSummarize) {
     napi_value o, v;
@@ -863,6 +896,80 @@ napi_value SummaryBlobs(napi_env env, napi_callback_info info) {
   return o;
 }
 
+// summarizeMap(ctx, quotedKeys, values, threads) -> Promise<timing>: the SharedMap summary of every document
+// of the last sparse map replay (fmt_map_summarize: device ordering and blob split, host JSON threads);
+// read them with mapSummaryBlobs. Rejects with FMT_E_UNSUPPORTED when the loaded libfmt lacks the call.
+napi_value SummarizeMap(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  if (argc < 4 || !get_ctx(env, argv[0], &c)) return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "summarizeMap: a replay is running on this context");
+    return nullptr;
+  }
+  auto* j = new Job;
+  j->c = c;
+  j->kind = Job::kSummarizeMap;
+  if (!get_strings(env, argv[1], "keys", &j->keys) || !get_strings(env, argv[2], "values", &j->values) ||
+      !get_u32(env, argv[3], "threads", &j->threads)) {
+    delete j;
+    return nullptr;
+  }
+  return queue(env, j, argv[0], "fmtSummarizeMap");
+}
+
+// mapSummaryBlobs(ctx, doc) -> {header, blobs: [blob0, ...]}: document doc's summary of the last summarizeMap
+// (throws with the document's status, or FMT_E_UNSUPPORTED, when it has none).
+napi_value MapSummaryBlobs(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  if (argc < 2 || !get_ctx(env, argv[0], &c)) return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "mapSummaryBlobs: a replay is running on this context");
+    return nullptr;
+  }
+  uint32_t doc;
+  if (!get_u32(env, argv[1], "doc", &doc)) return nullptr;
+  using BlobsFn = decltype(&fmt_map_summary_blobs);
+  using BlobFn = decltype(&fmt_map_summary_blob);
+  const BlobsFn blobs = reinterpret_cast<BlobsFn>(libfmt_symbol("fmt_map_summary_blobs"));
+  const BlobFn blob = reinterpret_cast<BlobFn>(libfmt_symbol("fmt_map_summary_blob"));
+  if (blobs == nullptr || blob == nullptr) {
+    throw_fmt(env, FMT_E_UNSUPPORTED, "mapSummaryBlobs: this libfmt has no fmt_map_summary_blobs");
+    return nullptr;
+  }
+  const char* h = nullptr;
+  size_t hl = 0;
+  uint32_t n = 0;
+  int rc = blobs(c->ctx, doc, &h, &hl, &n);
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  napi_value o, v, arr;
+  napi_create_object(env, &o);
+  CHECK_NAPI(env, napi_create_string_utf8(env, h, hl, &v));
+  napi_set_named_property(env, o, "header", v);
+  CHECK_NAPI(env, napi_create_array_with_length(env, n, &arr));
+  for (uint32_t k = 0; k < n; k++) {
+    const char* b = nullptr;
+    size_t bl = 0;
+    rc = blob(c->ctx, doc, k, &b, &bl);
+    if (rc != FMT_OK) {
+      throw_fmt(env, rc, fmt_last_error(c->ctx));
+      return nullptr;
+    }
+    CHECK_NAPI(env, napi_create_string_utf8(env, b, bl, &v));
+    napi_set_element(env, arr, k, v);
+  }
+  napi_set_named_property(env, o, "blobs", arr);
+  return o;
+}
+
 // fetchDoc(ctx, doc, nLeaves, nChars, nProps) -> {leaves: ArrayBuffer, chars: ArrayBuffer, props: ArrayBuffer}
 napi_value FetchDoc(napi_env env, napi_callback_info info) {
   size_t argc = 5;
@@ -1140,6 +1247,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"replayMapSparse", nullptr, ReplayMapSparse, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"summarizeLegacy", nullptr, SummarizeLegacy, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"summaryBlobs", nullptr, SummaryBlobs, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      // fmt_map_summary.h's pair, resolved in the loaded libfmt at the call. Not enumerable: Object.keys of the
+      // addon stays the list of fmt.h's entry points that tests/test_napi.py pins.
+      {"summarizeMap", nullptr, SummarizeMap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"mapSummaryBlobs", nullptr, MapSummaryBlobs, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof fns / sizeof fns[0], fns);
   napi_value sizes, v;

@@ -205,6 +205,11 @@ class FmtSummaryTiming(ctypes.Structure):  # fmt_summary_timing
                 ("bytes", ctypes.c_uint64), ("threads", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+class FmtMapSummaryTiming(ctypes.Structure):  # fmt_map_summary_timing (include/fmt_map_summary.h)
+    _fields_ = [("kernel_ms", ctypes.c_double), ("fetch_ms", ctypes.c_double), ("format_ms", ctypes.c_double),
+                ("bytes", ctypes.c_uint64), ("threads", ctypes.c_uint32), ("host_ordered_docs", ctypes.c_uint32)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"fmt error {STATUS_NAMES.get(code, code)}: {msg}")
@@ -260,7 +265,14 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_summary_v1_blobs", [P, U32, ctypes.POINTER(ctypes.c_char_p),
                                                         ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(U32)]),
                            ("fmt_mt_summary_v1_body", [P, U32, U32, ctypes.POINTER(ctypes.c_char_p),
-                                                       ctypes.POINTER(ctypes.c_size_t)])):
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+                           ("fmt_map_summarize", [P, P, U32, P, U32, U32, ctypes.POINTER(FmtMapSummaryTiming)]),
+                           ("fmt_map_summary_blobs", [P, U32, ctypes.POINTER(ctypes.c_char_p),
+                                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(U32)]),
+                           ("fmt_map_summary_blob", [P, U32, U32, ctypes.POINTER(ctypes.c_char_p),
+                                                     ctypes.POINTER(ctypes.c_size_t)]),
+                           ("fmt_internal_map_summary_arrays", [P, P, P, P, U64]),
+                           ("fmt_internal_map_summary_host_only", [P, ctypes.c_int])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
                 getattr(L, name).argtypes = args
         _libs[path] = L
@@ -283,6 +295,10 @@ EXPORTED_SYMBOLS = [
 EXPORTED_SYMBOLS_V1 = ["fmt_mt_summarize_v1", "fmt_mt_summary_v1_blobs", "fmt_mt_summary_v1_body"]
 # include/fmt_map_tiered.h (the sparse map path with its HBM tier)
 EXPORTED_SYMBOLS_MAP_TIERED = ["fmt_map_run_sparse_tiered"]
+# include/fmt_map_summary.h (bulk SharedMap summaries of the sparse path)
+EXPORTED_SYMBOLS_MAP_SUMMARY = ["fmt_map_summarize", "fmt_map_summary_blobs", "fmt_map_summary_blob"]
+MAP_SUMMARY_CONTENT = 0xFFFFFFFF    # tag of an ordered entry that stays in the header's "content"
+MAP_SUMMARY_DEVICE_MAX = 2048       # live entries per document the device tier orders (csrc/map_sum_plan.h)
 
 
 def _c_strings(strs):
@@ -346,6 +362,59 @@ def legacy_format(runs, text, propsets, keys, values, min_seq, chunk=10000, numb
     e = [0] + list((ctypes.c_uint64 * n.value).from_address(ends.value))
     blobs = [ctypes.string_at(out.value + e[k], e[k + 1] - e[k]).decode("utf-8") for k in range(n.value)]
     return blobs[0], (blobs[1] if len(blobs) > 1 else None)
+
+
+def _map_summary_host(counts, entries, keys, values, threads):
+    from .streams import js_quote
+
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    entries = np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE)
+    n = int(counts.sum(dtype=np.uint64))
+    if len(entries) < n:
+        raise ValueError("fewer entries than counts name")
+    ka, nk = _c_strings(js_quote(k) for k in keys)
+    va, nv = _c_strings(values)
+    ordered = np.zeros(max(n, 1), dtype=MAP_ENTRY_DTYPE)
+    tags = np.zeros(max(n, 1), dtype=np.uint32)
+    n_blobs = np.zeros(max(len(counts), 1), dtype=np.uint32)
+    status = np.zeros(max(len(counts), 1), dtype=np.int32)
+    P, U32 = ctypes.c_void_p, ctypes.c_uint32
+    f = lib().fmt_internal_map_summary_format
+    f.argtypes = [P, P, U32, P, U32, P, U32, U32, P, P, P, P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)]
+    docs, piece_at, ends = P(), P(), P()
+    rc = f(_ptr(counts), _ptr(entries), len(counts), ka, nk, va, nv, threads, _ptr(ordered), _ptr(tags), _ptr(n_blobs),
+           _ptr(status), ctypes.byref(docs), ctypes.byref(piece_at), ctypes.byref(ends))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_map_summary_format")
+    nd = len(counts)
+    out = []
+    if nd:
+        at = np.ctypeslib.as_array(ctypes.cast(piece_at, ctypes.POINTER(ctypes.c_uint64)), (nd + 1,))
+        ptrs = np.ctypeslib.as_array(ctypes.cast(docs, ctypes.POINTER(ctypes.c_uint64)), (nd,))
+        e = np.ctypeslib.as_array(ctypes.cast(ends, ctypes.POINTER(ctypes.c_uint64)), (max(int(at[nd]), 1),))
+        for d in range(nd):
+            if status[d] != FMT_OK:
+                out.append(EngineError(int(status[d]), f"document {d}: a key or value id outside the tables"))
+                continue
+            cut = [0] + [int(x) for x in e[int(at[d]) : int(at[d + 1])]]
+            pieces = [ctypes.string_at(int(ptrs[d]) + cut[k], cut[k + 1] - cut[k]).decode("utf-8") for k in range(len(cut) - 1)]
+            out.append((pieces[0], pieces[1:]))
+    return out, ordered[:n], tags[:n], n_blobs[:nd], status[:nd]
+
+
+def map_summary_format(counts, entries, keys, values, threads: int = 0):
+    """fmt_internal_map_summary_format: fmt_map_summarize's host half (csrc/map_sum_plan.h: tables, JS
+    object order, blob scan, formatter) over fetched sparse entries (Engine.map_fetch_sparse's counts and
+    birth-ordered entries), no device needed. Returns one item per document: (header, [blob0, ...]), or
+    an EngineError (not raised) for a document with a key or value id outside `keys` / `values`."""
+    return _map_summary_host(counts, entries, keys, values, threads)[0]
+
+
+def map_summary_order(counts, entries, keys, values, threads: int = 0):
+    """The same hook's arrays: (ordered entries, tags, n_blobs[n_docs], status[n_docs]), the entries of
+    all documents packed in document order, each document's in summary order; tags[i] is the blob the
+    entry lands in, MAP_SUMMARY_CONTENT for the header. What Engine.map_summary_arrays is compared to."""
+    return _map_summary_host(counts, entries, keys, values, threads)[1:]
 
 
 class MtPlanResult:
@@ -538,6 +607,46 @@ class Engine:
         self._check(self.L.fmt_map_pending_fetch(self.h, _ptr(counts), _ptr(status), _ptr(entries), n.value,
                                                  ctypes.byref(n)))
         return counts, status, entries[: n.value]
+
+    # ---- bulk summaries of the last sparse map run (include/fmt_map_summary.h)
+    def map_summarize(self, keys, values, threads: int = 0) -> dict:
+        """fmt_map_summarize: every document's SharedMap summary from the sequenced entries of the last
+        map_run_sparse / map_run_sparse_tiered (device ordering and blob split, host JSON); keys / values:
+        MapBatch.keys / .values. Returns the timing. Blobs: map_summary_doc(doc)."""
+        from .streams import js_quote
+
+        ka, nk = _c_strings(js_quote(k) for k in keys)
+        va, nv = _c_strings(values)
+        t = FmtMapSummaryTiming()
+        self._check(self.L.fmt_map_summarize(self.h, ka, nk, va, nv, threads, ctypes.byref(t)))
+        return {"kernel_ms": t.kernel_ms, "fetch_ms": t.fetch_ms, "format_ms": t.format_ms, "bytes": int(t.bytes),
+                "threads": int(t.threads), "host_ordered_docs": int(t.host_ordered_docs)}
+
+    def map_summary_doc(self, doc: int):
+        """(header, [blob0, ...]) of document `doc` from the last map_summarize; EngineError with the
+        document's status when it has none."""
+        h, hl, n = ctypes.c_char_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        self._check(self.L.fmt_map_summary_blobs(self.h, doc, ctypes.byref(h), ctypes.byref(hl), ctypes.byref(n)))
+        head = ctypes.string_at(h, hl.value).decode("utf-8")
+        blobs = []
+        for k in range(n.value):
+            b, bl = ctypes.c_char_p(), ctypes.c_size_t()
+            self._check(self.L.fmt_map_summary_blob(self.h, doc, k, ctypes.byref(b), ctypes.byref(bl)))
+            blobs.append(ctypes.string_at(b, bl.value).decode("utf-8"))
+        return head, blobs
+
+    def map_summary_arrays(self, n_entries: int):
+        """Test hook: (ordered entries, tags, n_blobs) of the last map_summarize as fetched from the device,
+        the layout of native.map_summary_order; n_entries: the batch's live entries (sum of the counts)."""
+        ordered = np.zeros(max(n_entries, 1), dtype=MAP_ENTRY_DTYPE)
+        tags = np.zeros(max(n_entries, 1), dtype=np.uint32)
+        n_blobs = np.zeros(max(self._map_shape[0], 1), dtype=np.uint32)
+        self._check(self.L.fmt_internal_map_summary_arrays(self.h, _ptr(ordered), _ptr(tags), _ptr(n_blobs), n_entries))
+        return ordered[:n_entries], tags[:n_entries], n_blobs[: self._map_shape[0]]
+
+    def map_summary_host_only(self, on: bool):
+        """Measurement switch (tools/bench_map_summary.py): map_summarize orders every document on the host."""
+        self._check(self.L.fmt_internal_map_summary_host_only(self.h, int(on)))
 
     # ---- bulk legacy summaries of the last merge-tree run
     def mt_summarize_legacy(self, keys, values, chunk: int = 10000, threads: int = 0) -> dict:

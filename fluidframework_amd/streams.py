@@ -159,6 +159,8 @@ def js_quote(s: str) -> str:
     surrogates are escaped as \\udXXX, which json.dumps(ensure_ascii=False) would write raw). A high
     and a low surrogate that two concatenated Python strings left side by side are one code point
     to JavaScript, whose strings are UTF-16: they are written as that character, not as two escapes."""
+    if s.isascii() and s.isalnum():  # (nothing to escape: the bulk summaries quote 10^6 such keys per call)
+        return '"' + s + '"'
     if _SURROGATE.search(s):
         s = s.encode("utf-16-le", "surrogatepass").decode("utf-16-le", "surrogatepass")
     out = ['"']

@@ -152,6 +152,9 @@ int planMergeTreeLoad(const fmt_mt_batch* b, const Caps& large, MtPlan& out, con
   const uint32_t n = b->n_docs;
   if (b->doc_op_offsets[0] != 0 || b->doc_op_offsets[n] != b->n_ops)
     return refuse(FMT_E_USAGE, "doc_op_offsets do not cover ops");
+  // (a document's op count is offsets[d + 1] - offsets[d] on the device: a descending pair would wrap)
+  for (uint32_t d = 0; d < n; d++)
+    if (b->doc_op_offsets[d + 1] < b->doc_op_offsets[d]) return refuse(FMT_E_USAGE, "doc_op_offsets not ascending");
   MtPlan P;
   // one pass over the op records on host threads: totals, and the first invalid record
   struct OpScan {

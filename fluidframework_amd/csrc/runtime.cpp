@@ -125,6 +125,8 @@ struct fmt_ctx {
   uint64_t mapNOps = 0;
   uint32_t mapDocs = 0, mapKeyBound = 0;
   bool mapLoaded = false;
+  bool mapRan = false;     // fmt_map_run was issued for the loaded (dense) batch
+  bool mapErrValid = false;  // errWord holds the word of a map run (staged, sparse or fmt_map_replay_device)
   // SharedMap, sparse path: entries at each document's op offset, live counts, packed copy
   DevBuf<fmt_map_entry> mapEntries, mapPacked;
   DevBuf<uint32_t> mapCounts;
@@ -214,6 +216,7 @@ struct fmt_ctx {
   // documents refused at load (a feature the huge tier lacks, or no device memory for its state):
   // their headers are written at load and no tier runs them; the rest of the batch is unaffected
   std::vector<uint32_t> mtRefused;
+  std::vector<fmt_mt_doc_result> mtRefusedHdr;  // their headers, parallel (fmt_mt_fetch_headers before a run)
   bool mtUseList = false;                    // the small tiers run mtSmallList (huge or refused docs)
   uint32_t mtGrown = 0;                      // documents the last run escalated into the huge tier
   std::vector<uint64_t> mtOffsHost;          // host copies of doc_op_offsets and the snapshot docs
@@ -284,6 +287,12 @@ namespace {
 int setErr(fmt_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   return code;
+}
+
+// Call order (fmt.h): what a fetch, digest or summary reads is written by fmt_mt_run. After a load and
+// before a run the result buffers hold an earlier batch, or nothing; the call is refused on the host.
+int mtNeedsRun(fmt_ctx* c, const char* what) {
+  return setErr(c, FMT_E_USAGE, std::string(what) + " before fmt_mt_run: no run has completed since the last fmt_mt_load");
 }
 
 int hipErr(fmt_ctx* c, hipError_t e, const char* what) {
@@ -537,8 +546,10 @@ static int mapValidate(fmt_ctx* c, const fmt_map_op* ops, uint64_t nOps, const u
   if (c == nullptr || (nOps > 0 && ops == nullptr) || offs == nullptr || keyBound == 0)
     return setErr(c, FMT_E_USAGE, "fmt_map_load: bad arguments");
   if (offs[0] != 0 || offs[nDocs] != nOps) return setErr(c, FMT_E_USAGE, "doc_op_offsets do not cover ops");
-  for (uint32_t d = 0; d < nDocs; d++) {
+  // (all of them before any op is read: with both ends checked, ascending offsets stay inside `ops`)
+  for (uint32_t d = 0; d < nDocs; d++)
     if (offs[d + 1] < offs[d]) return setErr(c, FMT_E_USAGE, "doc_op_offsets not monotone");
+  for (uint32_t d = 0; d < nDocs; d++) {
     // seq 0 is the dense kernels' "no kill yet / no set yet" (map_lww.hip): a set at seq 0 would be dropped
     if (offs[d + 1] > offs[d] && ops[offs[d]].seq == 0) {
       char m[96];
@@ -576,6 +587,8 @@ static int mapStage(fmt_ctx* c, const fmt_map_op* ops, uint64_t nOps, const uint
   c->mapKeyBound = keyBound;
   c->mapLoaded = true;
   c->mapSparse = sparse;
+  c->mapRan = false;
+  c->mapErrValid = false;
   c->mapSparseRan = false;
   c->mapPendRan = false;
   c->mapTieredDone = false;
@@ -599,6 +612,8 @@ int fmt_map_load_sparse(fmt_ctx* c, const fmt_map_op* ops, uint64_t nOps, const 
 
 int fmt_map_run_sparse(fmt_ctx* c) {
   if (c == nullptr || !c->mapLoaded || !c->mapSparse) return setErr(c, FMT_E_USAGE, "fmt_map_run_sparse before fmt_map_load_sparse");
+  c->mapSparseRan = false;  // (until this run is issued: a device error leaves no run to fetch)
+  c->mapErrValid = false;
   FMT_HIP(c, hipSetDevice(c->device));
   FMT_HIP(c, hipMemsetAsync(c->errWord.p, 0, sizeof(int), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -614,6 +629,7 @@ int fmt_map_run_sparse(fmt_ctx* c) {
   c->stats.bytes_written = static_cast<uint64_t>(c->mapDocs) * sizeof(uint32_t);  // + entries, at fetch
   c->stats.launches = 1;
   c->mapSparseRan = true;
+  c->mapErrValid = true;
   c->mapPendRan = false;
   c->mapTieredDone = false;
   return FMT_OK;
@@ -623,6 +639,8 @@ int fmt_map_run_sparse(fmt_ctx* c) {
 int fmt_map_run_sparse_tiered(fmt_ctx* c) {
   if (c == nullptr || !c->mapLoaded || !c->mapSparse)
     return setErr(c, FMT_E_USAGE, "fmt_map_run_sparse_tiered before fmt_map_load_sparse");
+  c->mapSparseRan = false;
+  c->mapErrValid = false;
   FMT_HIP(c, hipSetDevice(c->device));
   FMT_HIP(c, c->mapOvf.reserve(c->mapDocs + 1ull));
   FMT_HIP(c, hipMemsetAsync(c->errWord.p, 0, sizeof(int), c->stream));
@@ -640,6 +658,7 @@ int fmt_map_run_sparse_tiered(fmt_ctx* c) {
   c->stats.bytes_written = static_cast<uint64_t>(c->mapDocs) * sizeof(uint32_t);  // + entries, at fetch
   c->stats.launches = 1;
   c->mapSparseRan = true;  // (the LDS tier's documents are valid whatever becomes of the rest)
+  c->mapErrValid = true;
   c->mapPendRan = false;
   c->mapTieredDone = false;
   uint32_t nOvf = 0;
@@ -698,6 +717,13 @@ int fmt_map_run_sparse_tiered(fmt_ctx* c) {
 int fmt_map_fetch_sparse(fmt_ctx* c, uint32_t* counts, fmt_map_entry* entries, uint64_t capEntries, uint64_t* nEntries) {
   if (c == nullptr || counts == nullptr || !c->mapLoaded || !c->mapSparse)
     return setErr(c, FMT_E_USAGE, "fmt_map_fetch_sparse: nothing loaded");
+  if (!c->mapSparseRan) {
+    // Before a run (fmt.h "Call order"): the batch with no op applied, from the host. mapCounts still
+    // holds an earlier batch's counts, or nothing.
+    std::memset(counts, 0, c->mapDocs * sizeof(uint32_t));
+    if (nEntries) *nEntries = 0;
+    return FMT_OK;
+  }
   FMT_HIP(c, hipSetDevice(c->device));
   int errWord = 0;
   FMT_HIP(c, hipMemcpyAsync(&errWord, c->errWord.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -976,6 +1002,7 @@ static int runMap(fmt_ctx* c, const fmt_map_op* ops, const uint64_t* offs, uint3
   c->stats.bytes_read = nOps * sizeof(fmt_map_op) + (nDocs + 1ull) * sizeof(uint64_t);
   c->stats.bytes_written = nSlots * sizeof(fmt_map_slot);
   c->stats.launches = 1;
+  c->mapErrValid = true;
   if (scratch != nullptr) {
     // HBM-table path: three table fills (8 B slot + 4 B kill + 4 B first per slot) and the finish
     // pass (reads slot + first, writes the slot) on top of the op stream and the kernel's atomics
@@ -988,12 +1015,23 @@ static int runMap(fmt_ctx* c, const fmt_map_op* ops, const uint64_t* offs, uint3
 
 int fmt_map_run(fmt_ctx* c) {
   if (c == nullptr || !c->mapLoaded || c->mapSparse) return setErr(c, FMT_E_USAGE, "fmt_map_run before fmt_map_load");
-  return runMap(c, c->mapOps.p, c->mapOffs.p, c->mapDocs, c->mapKeyBound, c->mapNOps, c->mapOut.p);
+  c->mapRan = false;
+  c->mapErrValid = false;
+  const int rc = runMap(c, c->mapOps.p, c->mapOffs.p, c->mapDocs, c->mapKeyBound, c->mapNOps, c->mapOut.p);
+  c->mapRan = rc == FMT_OK;
+  return rc;
 }
 
 int fmt_map_fetch(fmt_ctx* c, fmt_map_slot* out) {
   if (c == nullptr || out == nullptr || !c->mapLoaded || c->mapSparse)
     return setErr(c, FMT_E_USAGE, "fmt_map_fetch: nothing loaded");
+  if (!c->mapRan) {
+    // Before a run (fmt.h "Call order"): the batch with no op applied, from the host. mapOut still
+    // holds an earlier batch's slots, or nothing.
+    const size_t nSlots = static_cast<size_t>(c->mapDocs) * c->mapKeyBound;
+    for (size_t i = 0; i < nSlots; i++) out[i] = fmt_map_slot{FMT_MAP_ABSENT, 0u};
+    return FMT_OK;
+  }
   int errWord = 0;
   FMT_HIP(c, hipMemcpyAsync(&errWord, c->errWord.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   FMT_HIP(c, hipMemcpyAsync(out, c->mapOut.p, static_cast<size_t>(c->mapDocs) * c->mapKeyBound * sizeof(fmt_map_slot),
@@ -1015,6 +1053,8 @@ int fmt_map_replay_device(fmt_ctx* c, const fmt_map_op* dOps, const uint64_t* dO
 
 int fmt_map_check(fmt_ctx* c) {
   if (c == nullptr) return FMT_E_USAGE;
+  if (!c->mapErrValid)
+    return setErr(c, FMT_E_USAGE, "fmt_map_check before a map run (fmt_map_run, fmt_map_run_sparse[_tiered] or fmt_map_replay_device) since the last map load");
   int errWord = 0;
   FMT_HIP(c, hipMemcpyAsync(&errWord, c->errWord.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   FMT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1427,6 +1467,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   c->huge.clear();
   c->mtHugeSlot.assign(n, -1);
   c->mtRefused = P.refused;
+  c->mtRefusedHdr.clear();
   refusedHdr = P.refusedHdr;
   for (uint32_t d : P.hugeDocs) {
     const fmt_mt_snapshot_doc& sd = b->snapshots[d];
@@ -1442,6 +1483,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   }
   for (size_t i = 0; i < c->mtRefused.size(); i++)
     FMT_HIP(c, cp(c->mtHdr.p + c->mtRefused[i], &refusedHdr[i], sizeof(fmt_mt_doc_result)));
+  c->mtRefusedHdr = refusedHdr;
   c->mtHugeLoaded = static_cast<uint32_t>(c->huge.size());
   // the small tiers run the other documents from a list
   c->mtUseList = !c->huge.empty() || !c->mtRefused.empty();
@@ -1463,6 +1505,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
 
 int fmt_mt_run(fmt_ctx* c) {
   if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
+  c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
   FMT_HIP(c, hipSetDevice(c->device));
   // documents an earlier run of this load escalated into the huge tier start over: their state is
   // released, and only the load-time huge documents (c->mtHugeLoaded) run with the small tiers
@@ -1626,8 +1669,15 @@ int fmt_mt_run(fmt_ctx* c) {
 
 int fmt_mt_fetch_headers(fmt_ctx* c, fmt_mt_doc_result* out) {
   if (c == nullptr || out == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_headers: nothing loaded");
-  FMT_HIP(c, hipMemcpyAsync(out, c->mtHdr.p, c->mtDocs * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  if (!c->mtRan) {
+    // Before a run (fmt.h "Call order"): what the load decided, from the host. mtHdr still holds an
+    // earlier batch's headers, or nothing.
+    std::memset(out, 0, c->mtDocs * sizeof(fmt_mt_doc_result));
+    for (size_t i = 0; i < c->mtRefused.size(); i++) out[c->mtRefused[i]] = c->mtRefusedHdr[i];
+  } else {
+    FMT_HIP(c, hipMemcpyAsync(out, c->mtHdr.p, c->mtDocs * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+  }
   uint64_t w = static_cast<uint64_t>(c->mtDocs) * sizeof(fmt_mt_doc_result);
   int status = FMT_OK;
   for (uint32_t d = 0; d < c->mtDocs; d++) {
@@ -1646,6 +1696,7 @@ int fmt_mt_fetch_headers(fmt_ctx* c, fmt_mt_doc_result* out) {
 int fmt_mt_fetch_doc(fmt_ctx* c, uint32_t doc, fmt_mt_leaf* leaves, uint32_t capLeaves, uint16_t* chars,
                      uint32_t capChars, fmt_mt_propset* props, uint32_t capProps) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_doc: bad doc");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_doc");
   const int32_t hslot = doc < c->mtHugeSlot.size() ? c->mtHugeSlot[doc] : -1;
   if (hslot >= 0) {  // a huge document: its own output buffers
     const fmt_kernels::HugeOut& O = c->huge[static_cast<size_t>(hslot)].out;
@@ -1988,6 +2039,7 @@ void docViews(const fmt_ctx* c, std::vector<fmt_kernels::SumView>& views) {
 
 int fmt_mt_state_digest(fmt_ctx* c, uint64_t* out) {
   if (c == nullptr || out == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_state_digest: nothing loaded");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_state_digest");
   FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
   std::vector<fmt_kernels::SumView> views;
@@ -2005,6 +2057,7 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
                             uint32_t nValues, uint32_t chunk, uint32_t threads, fmt_summary_timing* timing) {
   if (c == nullptr || !c->mtLoaded || (nKeys && keys == nullptr) || (nValues && values == nullptr))
     return setErr(c, FMT_E_USAGE, "fmt_mt_summarize_legacy: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_summarize_legacy");
   using clk = std::chrono::steady_clock;
   FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
@@ -2320,6 +2373,7 @@ int fmt_mt_summary_v1_body(fmt_ctx* c, uint32_t doc, uint32_t k, const char** bo
 int fmt_mt_fetch_catchup(fmt_ctx* c, uint32_t doc, fmt_mt_catchup_range* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_catchup: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_catchup");
   if (!c->mtPlan.hasCatchup()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
@@ -2331,6 +2385,7 @@ int fmt_mt_fetch_catchup(fmt_ctx* c, uint32_t doc, fmt_mt_catchup_range* out, ui
 int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range* out, uint64_t cap) {
   if (c == nullptr || !c->mtLoaded || offsets == nullptr)
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_catchup_all: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_catchup_all");
   FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
   offsets[0] = 0;
@@ -2368,6 +2423,7 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_remove_order");
   if (!c->mtPlan.hasRmOrder()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
@@ -2380,6 +2436,7 @@ int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out
 static int fetchRmClientsHi(fmt_ctx* c, uint32_t doc, uint64_t* out, uint32_t cap, bool upper, const char* what) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, std::string(what) + ": bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, what);
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t per = upper ? fmt_huge::kHiOutWords - 1 : 1;
@@ -2408,6 +2465,7 @@ int fmt_mt_fetch_rm_clients_hi2(fmt_ctx* c, uint32_t doc, uint64_t* out, uint32_
 int fmt_mt_fetch_legacy_props(fmt_ctx* c, uint32_t doc, uint16_t* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_legacy_props: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_legacy_props");
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t m = h.n_leaves < cap ? h.n_leaves : cap;
@@ -2429,6 +2487,7 @@ int fmt_mt_fetch_legacy_props(fmt_ctx* c, uint32_t doc, uint16_t* out, uint32_t 
 int fmt_mt_fetch_numbers(fmt_ctx* c, uint32_t doc, double* out, uint32_t cap, uint32_t* nOut) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_numbers: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_numbers");
   uint32_t n = 0;
   if (c->mtPlan.anyAdjust) FMT_HIP(c, hipMemcpy(&n, c->mtNumCount.p + doc, sizeof n, hipMemcpyDeviceToHost));
   if (nOut) *nOut = n;
@@ -2441,6 +2500,7 @@ int fmt_mt_fetch_regen(fmt_ctx* c, uint32_t doc, fmt_mt_op* ops, uint32_t capOps
                        uint32_t* nOps, uint32_t* nText) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (ops == nullptr && capOps > 0) || (text == nullptr && capText > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_regen: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_regen");
   uint32_t cnt[2] = {0, 0};
   if (c->mtPlan.local) FMT_HIP(c, hipMemcpy(cnt, c->mtLocRegenCount.p + 2ull * doc, sizeof cnt, hipMemcpyDeviceToHost));
   if (nOps) *nOps = cnt[0];

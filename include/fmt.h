@@ -20,6 +20,16 @@
  *   - Inputs are caller-owned and only read during the call. Device state is library-owned until
  *     fmt_close(). No exception ever crosses this ABI. One context per host thread.
  *   - Positions and lengths are UTF-16 code units (textSegment.ts:60), exactly like JS strings.
+ *   - Call order. A context serves one batch after another and keeps its buffers, so what a fetch
+ *     reads belongs to the loaded batch only once a run has completed for it. Between a successful
+ *     load and the next completed run, every fetch, digest and summarize call of that family returns
+ *     FMT_E_USAGE (checked on the host, before any device call), with three exceptions that return the
+ *     loaded batch with no op applied, built on the host: fmt_mt_fetch_headers (the headers of the
+ *     documents the load itself refused, every other header zero), fmt_map_fetch (every slot
+ *     FMT_MAP_ABSENT, birth_seq 0) and fmt_map_fetch_sparse (every count 0, no entries). A load that
+ *     fails validation changes nothing: the batch loaded before stays loaded, run and fetchable. The
+ *     blobs of a summarize call stay valid until the next summarize call of that kind (the map ones:
+ *     or the next map load), whatever is loaded or run in between.
  */
 #ifndef FMT_H_
 #define FMT_H_
@@ -469,7 +479,8 @@ int fmt_map_load(fmt_ctx* ctx, const fmt_map_op* ops, uint64_t n_ops,
 /* Replay the staged batch (asynchronous on the ctx stream). */
 int fmt_map_run(fmt_ctx* ctx);
 /* Copy results to host: out[d * key_bound + k]. Synchronizes the ctx stream. Replaces reading
- * MapKernel.sequencedData (mapKernel.ts:131) for get()/summarizeCore (map.ts:176-246). */
+ * MapKernel.sequencedData (mapKernel.ts:131) for get()/summarizeCore (map.ts:176-246). Before the first
+ * fmt_map_run of the loaded batch: every slot FMT_MAP_ABSENT (Call order, above). */
 int fmt_map_fetch(fmt_ctx* ctx, fmt_map_slot* out);
 /* Zero-copy variant on caller-owned DEVICE buffers (e.g. torch tensors), launched on the ctx stream.
  * For key_bound > 2560 (the HBM-table path) d_out must be 8-byte aligned (FMT_E_USAGE otherwise).
@@ -478,7 +489,9 @@ int fmt_map_fetch(fmt_ctx* ctx, fmt_map_slot* out);
 int fmt_map_replay_device(fmt_ctx* ctx, const fmt_map_op* d_ops, const uint64_t* d_doc_op_offsets,
                           uint32_t n_docs, uint32_t key_bound, fmt_map_slot* d_out);
 /* Synchronizes the ctx stream; FMT_E_DATA when an op of the last map run referenced a key id
- * >= key_bound (the remote op the reference would reject while processing it, mapKernel.ts:619-630). */
+ * >= key_bound (the remote op the reference would reject while processing it, mapKernel.ts:619-630).
+ * FMT_E_USAGE when no map run (fmt_map_run, fmt_map_run_sparse[_tiered], fmt_map_replay_device) was
+ * issued since the last map load. */
 int fmt_map_check(fmt_ctx* ctx);
 
 /* Sparse LWW for key pools of any size (key_bound up to 2^32 - 1): the per-key reductions run in
@@ -506,7 +519,8 @@ int fmt_map_run_sparse(fmt_ctx* ctx);
 /* fmt_map_run_sparse_tiered (fmt_map_tiered.h) is the same run followed by an HBM tier for the
  * documents this one refuses. */
 /* counts[d] = live entries of document d (n_docs entries); entries of all documents packed in
- * document order into `entries` (cap_entries; *n_entries = their total). Synchronizes. */
+ * document order into `entries` (cap_entries; *n_entries = their total). Synchronizes. Before the first
+ * sparse run of the loaded batch: every count 0 and no entries (Call order, above). */
 int fmt_map_fetch_sparse(fmt_ctx* ctx, uint32_t* counts, fmt_map_entry* entries, uint64_t cap_entries,
                          uint64_t* n_entries);
 
@@ -558,6 +572,7 @@ int fmt_map_pending_fetch(fmt_ctx* ctx, uint32_t* counts, int32_t* status, fmt_m
  * including updateSeqNumbers/setMinSeq (client.ts:1381-1391, mergeTree.ts:1147-1166) and zamboni
  * (zamboni.ts:33-213). Per-document errors land in fmt_mt_doc_result.status / fail_seq. */
 int fmt_mt_load(fmt_ctx* ctx, const fmt_mt_batch* batch);
+/* (doc_op_offsets must start at 0, end at n_ops and ascend: FMT_E_USAGE otherwise, as for the map loads) */
 /* Replays every loaded document and returns when it is done. Plain batches start in the compact tier
  * (256 leaves, 2048 UTF-16 units); a document about to outgrow a tier stops at an op boundary, saves
  * its state, and the next tier resumes it: the small tier (512 leaves, 6144 units), then the large
@@ -565,7 +580,11 @@ int fmt_mt_load(fmt_ctx* ctx, const fmt_mt_batch* batch);
  * start in the small tier, and a document that overflows inside an op replays again from its
  * inputs in the next tier. Stats cover every launch. */
 int fmt_mt_run(fmt_ctx* ctx);
-/* Per-document result headers for all docs (n_docs entries). Synchronizes the ctx stream. */
+/* Per-document result headers for all docs (n_docs entries). Synchronizes the ctx stream. Before the
+ * first fmt_mt_run of the loaded batch: the headers of the documents the load refused (status,
+ * fail_seq, cur_seq, min_seq), every other header zero, from the host (Call order, above). Every other
+ * fmt_mt_fetch_*, fmt_mt_state_digest and fmt_mt_summarize_* call needs a completed fmt_mt_run since
+ * the last fmt_mt_load (FMT_E_USAGE otherwise). */
 int fmt_mt_fetch_headers(fmt_ctx* ctx, fmt_mt_doc_result* out);
 /* One document's leaves (cap_leaves), chars (cap_chars) and prop sets (cap_props): the converged
  * segment list that getText (MergeTreeTextHelper.ts:28-87) and Client.summarize

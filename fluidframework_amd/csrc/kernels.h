@@ -6,6 +6,7 @@
 #include "../../include/fmt.h"
 #include "map_plan.h"
 #include "mt_bind.h"
+#include "text_plan.h"
 
 namespace fmt_kernels {
 
@@ -126,6 +127,15 @@ hipError_t launchGatherSpans(const GatherSpan* spans, uint32_t n, uint32_t* dst,
 // Per-document content digest of the converged state (digest.hip).
 hipError_t launchStateDigest(const fmt_mt_doc_result* hdrs, const SumView* views, uint32_t nDocs, uint64_t* out,
                              int numCUs, hipStream_t stream);
+
+// Bulk getText (text.hip; work items and the host scan between the passes: text_plan.h). One wave per
+// item. Pass 1 writes the units each item contributes; pass 2 copies them to packed + tileBase[item].
+hipError_t launchTextTileUnits(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
+                               uint32_t nItems, uint16_t placeholder, unsigned long long* tileUnits, int numCUs,
+                               hipStream_t stream);
+hipError_t launchTextGather(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
+                            uint32_t nItems, uint16_t placeholder, const unsigned long long* tileBase, uint16_t* packed,
+                            int numCUs, hipStream_t stream);
 
 struct MtCaps {
   uint32_t leaves, chars, props;

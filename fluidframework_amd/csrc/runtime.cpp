@@ -17,6 +17,7 @@
 #include "../../include/fmt.h"
 #include "../../include/fmt_map_summary.h"
 #include "../../include/fmt_map_tiered.h"
+#include "../../include/fmt_text.h"
 #include "../../include/fmt_v1.h"
 #include "huge_engine.h"
 #include "jsnum.h"
@@ -280,6 +281,17 @@ struct fmt_ctx {
   std::vector<std::string> v1Blobs;           // per document: header, then body_0, body_1, ...
   std::vector<std::vector<uint64_t>> v1Ends;  // per document: where each of those blobs ends in v1Blobs[d]
   std::vector<int32_t> v1Status;
+  // bulk getText (fmt_mt_fetch_text_all, text.hip): the work items (text_plan.h), the units per item,
+  // each item's base in the packed text, the packed text. Its own buffers: no summary reads or writes them.
+  fmt_plan::TextPlan textPlan;
+  std::vector<fmt_kernels::SumView> textViews;
+  std::vector<uint64_t> textOffs;               // the offsets of the cached pass 1 (n_docs + 1)
+  DevBuf<fmt_plan::TextItem> textItems;
+  DevBuf<unsigned long long> textUnits, textBases;
+  DevBuf<uint16_t> textPacked;
+  PinnedBuf<uint64_t> textHostUnits, textHostBases;
+  bool textSized = false;                       // pass 1 and the scan hold for textPlaceholder since the last run
+  uint16_t textPlaceholder = 0;
 };
 
 namespace {
@@ -496,6 +508,10 @@ void fmt_close(fmt_ctx* c) {
   c->packed.release();
   c->digests.release();
   c->v1Segs.release();
+  c->textItems.release();
+  c->textUnits.release();
+  c->textBases.release();
+  c->textPacked.release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -1290,6 +1306,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   const fmt_plan::MtPlan& P = c->mtPlan;
   c->mtLoaded = false;  // (from here on the context holds this batch or, after a device error, none)
   c->mtRan = false;
+  c->textSized = false;
   const uint32_t n = b->n_docs;
   const uint32_t nKv = b->props_off ? b->props_off[b->n_props_ops] : 0;
   // host arrays the asynchronous copies below read; the stream is drained before they go, on every way out
@@ -1506,6 +1523,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
 int fmt_mt_run(fmt_ctx* c) {
   if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
   c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
+  c->textSized = false;
   FMT_HIP(c, hipSetDevice(c->device));
   // documents an earlier run of this load escalated into the huge tier start over: their state is
   // released, and only the load-time huge documents (c->mtHugeLoaded) run with the small tiers
@@ -2420,6 +2438,69 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
   return FMT_OK;
 }
 
+uint32_t fmt_mt_text_tile_leaves(void) { return fmt_plan::kTextTileLeaves; }
+
+int fmt_mt_fetch_text_all(fmt_ctx* c, uint16_t placeholder, uint64_t* offsets, uint16_t* out, uint64_t cap) {
+  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
+    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_text_all: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_text_all");
+  FMT_HIP(c, hipSetDevice(c->device));
+  const uint32_t nd = c->mtDocs;
+  // every document's result buffers. sumViews is shared with the summaries and the digest, so it is
+  // uploaded again ahead of each of the two launches (textViews lives in the ctx: the copy is asynchronous)
+  auto uploadViews = [&]() -> hipError_t {
+    docViews(c, c->textViews);
+    const hipError_t e = c->sumViews.reserve(nd);
+    return e != hipSuccess ? e
+                           : hipMemcpyAsync(c->sumViews.p, c->textViews.data(), nd * sizeof(fmt_kernels::SumView),
+                                            hipMemcpyHostToDevice, c->stream);
+  };
+  if (!c->textSized || c->textPlaceholder != placeholder) {
+    // pass 1: the work items from the headers, the units each contributes, the scan on the host
+    c->textSized = false;
+    std::vector<fmt_mt_doc_result> hdr(nd);
+    FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+    fmt_plan::planTextTiles(hdr.data(), nd, fmt_plan::kTextTileLeaves, c->textPlan);
+    const size_t ni = c->textPlan.items.size();
+    if (ni > 0xFFFFFFFFull) return setErr(c, FMT_E_CAPACITY, "fmt_mt_fetch_text_all: more than 2^32 - 1 work items");
+    FMT_HIP(c, c->textItems.reserve(ni));
+    FMT_HIP(c, c->textUnits.reserve(ni));
+    FMT_HIP(c, c->textBases.reserve(ni));
+    FMT_HIP(c, c->textHostUnits.reserve(ni));
+    FMT_HIP(c, c->textHostBases.reserve(ni));
+    c->textOffs.assign(nd + 1ull, 0);
+    if (ni) {
+      FMT_HIP(c, uploadViews());
+      FMT_HIP(c, hipMemcpyAsync(c->textItems.p, c->textPlan.items.data(), ni * sizeof(fmt_plan::TextItem),
+                                hipMemcpyHostToDevice, c->stream));
+      FMT_HIP(c, fmt_kernels::launchTextTileUnits(c->mtHdr.p, c->sumViews.p, c->textItems.p, static_cast<uint32_t>(ni),
+                                                  placeholder, c->textUnits.p, c->numCUs, c->stream));
+      FMT_HIP(c, hipMemcpyAsync(c->textHostUnits.p, c->textUnits.p, ni * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+      FMT_HIP(c, hipStreamSynchronize(c->stream));
+      fmt_plan::textOffsets(c->textPlan, c->textHostUnits.p, c->textOffs.data(), c->textHostBases.p);
+      FMT_HIP(c, hipMemcpyAsync(c->textBases.p, c->textHostBases.p, ni * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+      FMT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing of this call is in flight past here)
+    }
+    c->textPlaceholder = placeholder;
+    c->textSized = true;
+  }
+  std::memcpy(offsets, c->textOffs.data(), (nd + 1ull) * sizeof(uint64_t));
+  const uint64_t total = c->textOffs[nd];
+  if (out == nullptr) return FMT_OK;
+  if (cap < total) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_text_all: cap below the units of the text");
+  if (total == 0) return FMT_OK;
+  // pass 2: every item's units to its base in the packed text, then one staged copy of exactly those
+  // (stagedCopy waits for the stream first and returns when the units are in `out`)
+  FMT_HIP(c, c->textPacked.reserve(total));
+  FMT_HIP(c, uploadViews());
+  FMT_HIP(c, fmt_kernels::launchTextGather(c->mtHdr.p, c->sumViews.p, c->textItems.p,
+                                           static_cast<uint32_t>(c->textPlan.items.size()), placeholder, c->textBases.p,
+                                           c->textPacked.p, c->numCUs, c->stream));
+  FMT_HIP(c, stagedCopy(c, out, c->textPacked.p, total * sizeof(uint16_t), false));
+  return FMT_OK;
+}
+
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
@@ -2574,6 +2655,31 @@ int fmt_internal_mt_plan(const fmt_mt_batch* b, const char** err, const uint64_t
   *out = w.data();
   *nWords = w.size();
   return rc;
+}
+
+// Test hook (not part of fmt_text.h): fmt_mt_fetch_text_all's host half (text_plan.h) over host headers,
+// no device needed. tile_leaves 0: the kernels' tile. Words: the number of items; the items (doc, first
+// leaf, leaves each); each document's first item (n_docs + 1); and, when tile_units (one per item, so
+// from a second call) is given, the offsets (n_docs + 1) and every item's base. Valid until the calling
+// thread's next call.
+int fmt_internal_text_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_t tileLeaves, const uint64_t* tileUnits,
+                           const uint64_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint64_t> w;
+  if ((nDocs && hdrs == nullptr) || out == nullptr || nWords == nullptr) return FMT_E_USAGE;
+  fmt_plan::TextPlan P;
+  fmt_plan::planTextTiles(hdrs, nDocs, tileLeaves, P);
+  w.assign(1, P.items.size());
+  for (const fmt_plan::TextItem& it : P.items) w.insert(w.end(), {it.doc, it.firstLeaf, it.nLeaves});
+  w.insert(w.end(), P.docFirst.begin(), P.docFirst.end());
+  if (tileUnits != nullptr) {
+    std::vector<uint64_t> offs(nDocs + 1ull), base(P.items.size() + 1);
+    fmt_plan::textOffsets(P, tileUnits, offs.data(), base.data());
+    w.insert(w.end(), offs.begin(), offs.end());
+    w.insert(w.end(), base.begin(), base.end() - 1);
+  }
+  *out = w.data();
+  *nWords = w.size();
+  return FMT_OK;
 }
 
 // Test hook (not part of fmt.h): the HBM map tier's host half (map_plan.h planMapLarge) over a batch's

@@ -1314,6 +1314,32 @@ class MergeTreeReplay {
 	getText(doc) {
 		return this.segments(doc).filter((s) => s.removedSeq === undefined && !s.marker).map((s) => s.text).join("");
 	}
+	/**
+	 * Every document's text in one device pass (fmt_mt_fetch_text_all): an array of strings, one per
+	 * document, equal to getText(doc) for each. placeholder (optional): one UTF-16 unit or a
+	 * one-unit string that every Marker contributes (getTextWithPlaceholders); 0 or absent: none.
+	 * A document that failed gives undefined (getText(doc) throws for it; this call does not).
+	 */
+	texts(placeholder) {
+		const ph = typeof placeholder === "string" ? placeholder.charCodeAt(0) || 0 : placeholder || 0;
+		const n = this.batch.nDocs;
+		const r = native().fetchTextAll(this.engine.ctx, n, ph);
+		const ov = new DataView(r.offsets);
+		const at = (d) => ov.getUint32(8 * d, true) + ov.getUint32(8 * d + 4, true) * 4294967296;
+		const units = new Uint16Array(r.text);
+		const out = new Array(n);
+		for (let d = 0; d < n; d++) {
+			if (this.header(d).status !== 0) {
+				out[d] = undefined;
+				continue;
+			}
+			const a = at(d), b = at(d + 1);
+			const parts = [];
+			for (let i = a; i < b; i += 8192) parts.push(String.fromCharCode.apply(null, units.subarray(i, Math.min(b, i + 8192))));
+			out[d] = parts.join("");
+		}
+		return out;
+	}
 	getLength(doc) {
 		return this.header(doc).visibleLength;
 	}

@@ -24,6 +24,8 @@
 //   fetchNumbers(ctx, doc) -> Float64Array                           fmt_mt_fetch_numbers
 //   fetchLegacyProps(ctx, doc, nLeaves) -> Uint16Array               fmt_mt_fetch_legacy_props
 //   fetchRmClientsHi(ctx, doc, nLeaves) -> BigUint64Array            fmt_mt_fetch_rm_clients_hi (ids 64..127)
+//   fetchRmClientsHi2(ctx, doc, nLeaves) -> BigUint64Array           fmt_mt_fetch_rm_clients_hi2 (ids 128..253)
+//   fetchTextAll(ctx, nDocs, placeholder) -> {offsets, text}         fmt_mt_fetch_text_all (fmt_text.h)
 //   fetchRegen(ctx, doc) -> {ops: ArrayBuffer, text: Uint16Array}     fmt_mt_fetch_regen (f4 reconnects)
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
 //   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
@@ -51,6 +53,7 @@
 #include "fmt.h"
 #include "fmt_map_summary.h"
 #include "fmt_map_tiered.h"
+#include "fmt_text.h"
 
 namespace {
 
@@ -1165,6 +1168,83 @@ napi_value FetchRmClientsHi(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+// fetchRmClientsHi2(ctx, doc, nLeaves) -> BigUint64Array(2 * nLeaves): per leaf, its remove clients
+// 128..191 (bit c - 128) and 192..253 (bit c - 192)
+napi_value FetchRmClientsHi2(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  if (argc < 3 || !get_ctx(env, argv[0], &c)) return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "fetchRmClientsHi2: a replay is running on this context");
+    return nullptr;
+  }
+  uint32_t doc, n;
+  if (!get_u32(env, argv[1], "doc", &doc) || !get_u32(env, argv[2], "nLeaves", &n)) return nullptr;
+  if (n > 0x7FFFFFFFu) {
+    throw_fmt(env, FMT_E_USAGE, "fetchRmClientsHi2: nLeaves out of range");
+    return nullptr;
+  }
+  void* p;
+  napi_value ab, arr;
+  CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(n) * 2 * sizeof(uint64_t), &p, &ab));
+  const int rc = n ? fmt_mt_fetch_rm_clients_hi2(c->ctx, doc, static_cast<uint64_t*>(p), 2 * n) : FMT_OK;
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  CHECK_NAPI(env, napi_create_typedarray(env, napi_biguint64_array, size_t(n) * 2, ab, 0, &arr));
+  return arr;
+}
+
+// fetchTextAll(ctx, nDocs, placeholder) -> {offsets: ArrayBuffer (nDocs + 1 uint64), text: ArrayBuffer (UTF-16
+// units)}: every document's text in one device pass (fmt_mt_fetch_text_all; nDocs = the loaded batch's
+// document count; placeholder 0: getText, else the unit every Marker contributes)
+napi_value FetchTextAll(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  uint32_t nd, ph;
+  if (argc < 3 || !get_ctx(env, argv[0], &c) || !get_u32(env, argv[1], "nDocs", &nd) ||
+      !get_u32(env, argv[2], "placeholder", &ph))
+    return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "fetchTextAll: a replay is running on this context");
+    return nullptr;
+  }
+  if (ph > 0xFFFFu) {
+    throw_fmt(env, FMT_E_USAGE, "fetchTextAll: placeholder is one UTF-16 unit");
+    return nullptr;
+  }
+  using Fn = int (*)(fmt_ctx*, uint16_t, uint64_t*, uint16_t*, uint64_t);
+  const Fn fetch = reinterpret_cast<Fn>(libfmt_symbol("fmt_mt_fetch_text_all"));
+  if (fetch == nullptr) {
+    throw_fmt(env, FMT_E_UNSUPPORTED, "fetchTextAll: the loaded libfmt has no fmt_mt_fetch_text_all");
+    return nullptr;
+  }
+  void *po = nullptr, *pt = nullptr;
+  napi_value ob = nullptr, tb = nullptr;
+  CHECK_NAPI(env, napi_create_arraybuffer(env, (size_t(nd) + 1) * sizeof(uint64_t), &po, &ob));
+  uint64_t* offs = static_cast<uint64_t*>(po);
+  int rc = fetch(c->ctx, static_cast<uint16_t>(ph), offs, nullptr, 0);
+  if (rc == FMT_OK) {
+    const uint64_t total = offs[nd];
+    CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(total) * sizeof(uint16_t), &pt, &tb));
+    if (total) rc = fetch(c->ctx, static_cast<uint16_t>(ph), offs, static_cast<uint16_t*>(pt), total);
+  }
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  napi_value o;
+  CHECK_NAPI(env, napi_create_object(env, &o));
+  CHECK_NAPI(env, napi_set_named_property(env, o, "offsets", ob));
+  CHECK_NAPI(env, napi_set_named_property(env, o, "text", tb));
+  return o;
+}
+
 napi_value FetchRegen(napi_env env, napi_callback_info info) {
   size_t argc = 2;
   napi_value argv[2];
@@ -1251,6 +1331,10 @@ napi_value Init(napi_env env, napi_value exports) {
       // addon stays the list of fmt.h's entry points that tests/test_napi.py pins.
       {"summarizeMap", nullptr, SummarizeMap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"mapSummaryBlobs", nullptr, MapSummaryBlobs, nullptr, nullptr, nullptr, napi_default, nullptr},
+      // fmt_text.h's bulk text read (resolved at the call, as above) and the second fetch of the high remove
+      // clients: not enumerable for the same reason
+      {"fetchTextAll", nullptr, FetchTextAll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"fetchRmClientsHi2", nullptr, FetchRmClientsHi2, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof fns / sizeof fns[0], fns);
   napi_value sizes, v;

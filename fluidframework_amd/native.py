@@ -271,10 +271,15 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(U32)]),
                            ("fmt_map_summary_blob", [P, U32, U32, ctypes.POINTER(ctypes.c_char_p),
                                                      ctypes.POINTER(ctypes.c_size_t)]),
+                           ("fmt_mt_fetch_text_all", [P, ctypes.c_uint16, P, P, U64]),
+                           ("fmt_mt_text_tile_leaves", []),
+                           ("fmt_internal_text_plan", [P, U32, U32, P, ctypes.POINTER(P), ctypes.POINTER(U64)]),
                            ("fmt_internal_map_summary_arrays", [P, P, P, P, U64]),
                            ("fmt_internal_map_summary_host_only", [P, ctypes.c_int])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
                 getattr(L, name).argtypes = args
+        if hasattr(L, "fmt_mt_text_tile_leaves"):
+            L.fmt_mt_text_tile_leaves.restype = U32
         _libs[path] = L
     return _libs[path]
 
@@ -297,6 +302,8 @@ EXPORTED_SYMBOLS_V1 = ["fmt_mt_summarize_v1", "fmt_mt_summary_v1_blobs", "fmt_mt
 EXPORTED_SYMBOLS_MAP_TIERED = ["fmt_map_run_sparse_tiered"]
 # include/fmt_map_summary.h (bulk SharedMap summaries of the sparse path)
 EXPORTED_SYMBOLS_MAP_SUMMARY = ["fmt_map_summarize", "fmt_map_summary_blobs", "fmt_map_summary_blob"]
+# include/fmt_text.h (bulk getText)
+EXPORTED_SYMBOLS_TEXT = ["fmt_mt_fetch_text_all", "fmt_mt_text_tile_leaves"]
 MAP_SUMMARY_CONTENT = 0xFFFFFFFF    # tag of an ordered entry that stays in the header's "content"
 MAP_SUMMARY_DEVICE_MAX = 2048       # live entries per document the device tier orders (csrc/map_sum_plan.h)
 
@@ -450,6 +457,54 @@ def mt_plan(batch, struct=None) -> MtPlanResult:
     r.loc_offs = r.loc_offs.reshape(6, -1) if len(r.loc_offs) else r.loc_offs
     r.start_seg = r.start_seg.reshape(-1, 3)
     r.refused = r.refused.view(np.int64).reshape(-1, 5)  # doc, status, fail_seq, cur_seq, min_seq
+    return r
+
+
+class TextPlanResult:
+    """What text_plan read back (csrc/text_plan.h): `items` ((n, 3): doc, first leaf, leaves), `doc_first`
+    (n_docs + 1: each document's first item) and, when tile units were given, `offsets` (n_docs + 1) and
+    `tile_base` (one per item)."""
+
+
+def text_tile_leaves() -> int:
+    """fmt_mt_text_tile_leaves: leaves per work item of the bulk text kernels."""
+    return int(lib().fmt_mt_text_tile_leaves())
+
+
+def text_plan(headers, tile_leaves: int = 0, tile_units=None) -> TextPlanResult:
+    """fmt_internal_text_plan: fmt_mt_fetch_text_all's host half over result headers (DOC_RESULT_DTYPE),
+    no device needed. tile_leaves 0: the kernels' tile. tile_units (one per work item): also the offsets
+    and tile bases their exclusive prefix gives."""
+    hdr = np.ascontiguousarray(headers, dtype=DOC_RESULT_DTYPE)
+    units = None if tile_units is None else np.ascontiguousarray(tile_units, dtype=np.uint64)
+    P = ctypes.c_void_p
+    out, n = P(), ctypes.c_uint64()
+    f = lib().fmt_internal_text_plan
+
+    def call(u):
+        rc = f(_ptr(hdr) if len(hdr) else None, len(hdr), tile_leaves, u, ctypes.byref(out), ctypes.byref(n))
+        if rc != FMT_OK:
+            raise EngineError(rc, "fmt_internal_text_plan")
+        return np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy()
+
+    w = call(None)
+    ni = int(w[0])
+    if units is not None:
+        if len(units) != ni:
+            raise ValueError(f"{len(units)} tile units for {ni} work items")
+        w = call(_ptr(units) if ni else _ptr(np.zeros(1, np.uint64)))
+    r = TextPlanResult()
+    r.items = w[1 : 1 + 3 * ni].reshape(ni, 3)
+    at = 1 + 3 * ni
+    r.doc_first = w[at : at + len(hdr) + 1]
+    at += len(hdr) + 1
+    r.offsets = r.tile_base = None
+    if units is not None:
+        r.offsets = w[at : at + len(hdr) + 1]
+        at += len(hdr) + 1
+        r.tile_base = w[at : at + ni]
+        at += ni
+    assert at == len(w)
     return r
 
 
@@ -731,6 +786,25 @@ class Engine:
         props = np.zeros(max(npp, 1), dtype=PROPSET_DTYPE)
         self._check(self.L.fmt_mt_fetch_doc(self.h, doc, _ptr(leaves), nl, _ptr(chars), nc, _ptr(props), npp))
         return leaves[:nl], chars[:nc], props[:npp]
+
+    # ---- bulk getText of the last merge-tree run (include/fmt_text.h)
+    def mt_texts(self, placeholder: int = 0):
+        """fmt_mt_fetch_text_all: every document's text from the local perspective in one device pass:
+        (offsets uint64[n_docs + 1], units uint16[total]), document d's units at
+        units[offsets[d]:offsets[d + 1]] (none for a document that failed). placeholder 0: getText();
+        otherwise getTextWithPlaceholders() with that UTF-16 unit for every Marker."""
+        offs = np.zeros(self._mt_docs + 1, dtype=np.uint64)
+        self._check(self.L.fmt_mt_fetch_text_all(self.h, placeholder, _ptr(offs), None, 0))
+        total = int(offs[-1])
+        units = np.zeros(max(total, 1), dtype="<u2")
+        self._check(self.L.fmt_mt_fetch_text_all(self.h, placeholder, _ptr(offs), _ptr(units), total))
+        return offs, units[:total]
+
+    def mt_text_strings(self, placeholder: int = 0) -> list:
+        """mt_texts as one str per document (lone surrogates kept: utf-16-le, surrogatepass)."""
+        offs, units = self.mt_texts(placeholder)
+        raw = units.tobytes()
+        return [raw[2 * int(a) : 2 * int(b)].decode("utf-16-le", "surrogatepass") for a, b in zip(offs[:-1], offs[1:])]
 
     def mt_digests(self) -> np.ndarray:
         """fmt_mt_state_digest: every document's 64-bit content digest."""

@@ -4363,11 +4363,17 @@ class HugeDocT {
       }
       if (sum != L->gStable[g]) return bad("group stable", sum, L->gStable[g]);
     }
-    if (nw != static_cast<long>(nWin)) bad("window count", nw, nWin);
+    if (nw != static_cast<long>(nWin)) return bad("window count", nw, nWin);
     for (uint32_t w = 0; w < nWin && w < kWinLds; w++) {  // the LDS mirror of the window table
       for (int f = 0; f < 4; f++)
         if (L->wRecL[4 * w + f] != S.wRec[4 * w + f]) return bad("window mirror", w, f);
       if (L->wMaskL[2 * w] != S.wMask[2 * w] || L->wMaskL[2 * w + 1] != S.wMask[2 * w + 1]) return bad("window mirror mask", w, 0);
+    }
+    // every entry, the HBM-only tail included, is the one its leaf points to (the per-leaf loop above
+    // reaches entries through winIdx: this is the other direction, a slot nobody points to)
+    for (uint32_t w = 0; w < nWin; w++) {
+      if (S.wLeaf[w] >= S.idCap) return bad("window entry leaf id", w, S.wLeaf[w]);
+      if (S.winIdx[S.wLeaf[w]] != w) return bad("window entry owner", w, S.winIdx[S.wLeaf[w]]);
     }
     for (int c = 0; c * 32 < nGroups; c++) {  // the group scan's chunk sums and positions
       long sum = 0;

@@ -141,12 +141,12 @@ def _writers40():
 def _huge(seed, first):
     """A summary-loaded document of 2,100 segments (past the large tier's 2,048 leaves) and 300 ops among
     300-op conflict-farm documents: first of 7, or seventh of 13."""
-    import test_gpu_huge
     from fluidframework_amd import workloads
+    from huge_edges import concat_batches
 
     farm = workloads.conflict_farm(6, n_clients=8, ops_per_doc=300, seed=seed)
     t3 = workloads.t3_stream(2100, 300, n_clients=8, max_lag=100, seed=seed + 1)
-    return test_gpu_huge._concat([t3, farm] if first else [farm, t3, farm])
+    return concat_batches([t3, farm] if first else [farm, t3, farm])
 
 
 def _summary_header(n_segs):

@@ -1,12 +1,12 @@
 """T3 on the GPU (BASELINE config 5): documents beyond the large tier are replayed by the huge-document
 engine (csrc/huge_engine.h, hugedoc.hip) through the same C ABI, bit-exact against the oracle (with
 its remote-length index): every leaf field, the text, the prop sets, the header."""
-import copy
-
 import numpy as np
 import pytest
 
 from fluidframework_amd import native, workloads
+from huge_edges import concat_batches as _concat
+from huge_edges import one_doc as _one_doc
 from mt_compare import compare_doc
 
 pytestmark = pytest.mark.gpu
@@ -31,51 +31,6 @@ def _oracle(orc, batch, doc=0, cap_props=4096):
     finally:
         orc.set_index(False)
     return rc, (h, lv[: int(h["n_leaves"])], ch[: int(h["n_chars"])], pr[: int(h["n_props"])])
-
-
-def _one_doc(batch, d):
-    b = copy.copy(batch)
-    o0, o1 = int(batch.doc_op_offsets[d]), int(batch.doc_op_offsets[d + 1])
-    b.ops = batch.ops[o0:o1]
-    b.doc_op_offsets = np.array([0, o1 - o0], dtype=np.uint64)
-    b.doc_init = batch.doc_init[d : d + 1]
-    if batch.snapshots is not None:
-        b.snapshots = batch.snapshots[d : d + 1]
-    return b
-
-
-def _concat(batches):
-    """One batch holding every document of `batches` (same props table: conflict farm and T3 share it)."""
-    from fluidframework_amd.streams import SNAPSHOT_DOC_DTYPE, SNAPSHOT_SEG_DTYPE
-
-    ops, offs, texts, init, snaps, segs = [], [0], [], [], [], []
-    tbase, sbase = 0, 0
-    for b in batches:
-        o = b.ops.copy()
-        o["payload"][o["type"] == 0] += tbase
-        ops.append(o)
-        offs.extend((np.asarray(b.doc_op_offsets[1:], dtype=np.int64) + offs[-1]).tolist())
-        texts.append(b.text)
-        di = b.doc_init.copy()
-        di[:, 0] += tbase
-        init.append(di)
-        if b.snapshots is not None:
-            sd = b.snapshots.copy()
-            sd["first_seg"] += sbase
-            sg = b.snapshot_segs.copy()
-            sg["text"] += tbase
-            snaps.append(sd)
-            segs.append(sg)
-            sbase += len(sg)
-        else:
-            snaps.append(np.zeros(b.n_docs, dtype=SNAPSHOT_DOC_DTYPE))
-        tbase += len(b.text)
-    first = batches[0]
-    return first.__class__(
-        ops=np.concatenate(ops), doc_op_offsets=np.asarray(offs, dtype=np.uint64), text=np.concatenate(texts),
-        doc_init=np.concatenate(init), props_off=first.props_off, props_kv=first.props_kv, keys=first.keys,
-        values=first.values, snapshots=np.concatenate(snaps),
-        snapshot_segs=np.concatenate(segs) if segs else np.zeros(0, dtype=SNAPSHOT_SEG_DTYPE))
 
 
 @pytest.mark.parametrize("segs,ops,clients,lag,rng,seed", [

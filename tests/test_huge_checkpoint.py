@@ -277,7 +277,7 @@ def test_large_to_huge_checkpoint_on_gpu(orc, grown):
     equal the oracle; the ordinary documents beside them replay as before."""
     from growth import growth_batch as gb
     from fluidframework_amd import workloads
-    from test_gpu_huge import _concat
+    from huge_edges import concat_batches as _concat
 
     farm = workloads.conflict_farm(16, n_clients=8, ops_per_doc=600, seed=3)
     batch = _concat([farm, grown, _ob_growth(), farm])

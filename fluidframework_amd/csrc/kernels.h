@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fmt.h"
+#include "../../include/fmt_runs.h"
 #include "map_plan.h"
 #include "mt_bind.h"
+#include "runs_plan.h"
 #include "text_plan.h"
 
 namespace fmt_kernels {
@@ -136,6 +138,20 @@ hipError_t launchTextTileUnits(const fmt_mt_doc_result* hdrs, const SumView* vie
 hipError_t launchTextGather(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
                             uint32_t nItems, uint16_t placeholder, const unsigned long long* tileBase, uint16_t* packed,
                             int numCUs, hipStream_t stream);
+
+// Bulk property runs (runs.hip; include/fmt_runs.h; the stitch between the passes: runs_plan.h). Work items
+// as above. clsOff[nDocs + 1]: each document's span of clsBuf, n_props entries, none for a document that
+// failed or carries SumView::cls. launchRunClasses fills clsBuf; launchRunTileReport writes one RunTile
+// per item; launchRunEmit writes the runs, every index below nRuns.
+hipError_t launchRunClasses(const fmt_mt_doc_result* hdrs, const SumView* views, uint32_t nDocs,
+                            const unsigned long long* clsOff, uint16_t* clsBuf, int numCUs, hipStream_t stream);
+hipError_t launchRunTileReport(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
+                               uint32_t nItems, const unsigned long long* clsOff, const uint16_t* clsBuf,
+                               fmt_plan::RunTile* tiles, int numCUs, hipStream_t stream);
+hipError_t launchRunEmit(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
+                         uint32_t nItems, const unsigned long long* clsOff, const uint16_t* clsBuf,
+                         const fmt_plan::RunTileBase* bases, uint64_t nRuns, fmt_mt_prop_run* runs, int numCUs,
+                         hipStream_t stream);
 
 struct MtCaps {
   uint32_t leaves, chars, props;

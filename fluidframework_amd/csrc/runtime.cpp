@@ -17,6 +17,7 @@
 #include "../../include/fmt.h"
 #include "../../include/fmt_map_summary.h"
 #include "../../include/fmt_map_tiered.h"
+#include "../../include/fmt_runs.h"
 #include "../../include/fmt_text.h"
 #include "../../include/fmt_v1.h"
 #include "huge_engine.h"
@@ -292,6 +293,22 @@ struct fmt_ctx {
   PinnedBuf<uint64_t> textHostUnits, textHostBases;
   bool textSized = false;                       // pass 1 and the scan hold for textPlaceholder since the last run
   uint16_t textPlaceholder = 0;
+  // bulk property runs (fmt_mt_fetch_prop_runs_all, runs.hip): the work items again (its own plan and copy:
+  // the text read's may belong to another placeholder's sizing call), each document's span of match
+  // classes, pass 1's report per item, the stitch's bases per item (runs_plan.h), the packed runs.
+  fmt_plan::TextPlan runsPlan;
+  std::vector<fmt_kernels::SumView> runsViews;
+  std::vector<uint64_t> runsOffs;               // the offsets of the cached sizing pass (n_docs + 1)
+  std::vector<uint64_t> runsClsOffs;            // n_docs + 1
+  DevBuf<fmt_plan::TextItem> runsItems;
+  DevBuf<unsigned long long> runsClsOff;
+  DevBuf<uint16_t> runsCls;
+  DevBuf<fmt_plan::RunTile> runsTiles;
+  DevBuf<fmt_plan::RunTileBase> runsBases;
+  DevBuf<fmt_mt_prop_run> runsPacked;
+  PinnedBuf<fmt_plan::RunTile> runsHostTiles;
+  PinnedBuf<fmt_plan::RunTileBase> runsHostBases;
+  bool runsSized = false;                       // classes, pass 1 and the stitch hold since the last run
 };
 
 namespace {
@@ -512,6 +529,12 @@ void fmt_close(fmt_ctx* c) {
   c->textUnits.release();
   c->textBases.release();
   c->textPacked.release();
+  c->runsItems.release();
+  c->runsClsOff.release();
+  c->runsCls.release();
+  c->runsTiles.release();
+  c->runsBases.release();
+  c->runsPacked.release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -1307,6 +1330,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   c->mtLoaded = false;  // (from here on the context holds this batch or, after a device error, none)
   c->mtRan = false;
   c->textSized = false;
+  c->runsSized = false;
   const uint32_t n = b->n_docs;
   const uint32_t nKv = b->props_off ? b->props_off[b->n_props_ops] : 0;
   // host arrays the asynchronous copies below read; the stream is drained before they go, on every way out
@@ -1524,6 +1548,7 @@ int fmt_mt_run(fmt_ctx* c) {
   if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
   c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
   c->textSized = false;
+  c->runsSized = false;
   FMT_HIP(c, hipSetDevice(c->device));
   // documents an earlier run of this load escalated into the huge tier start over: their state is
   // released, and only the load-time huge documents (c->mtHugeLoaded) run with the small tiers
@@ -2501,6 +2526,107 @@ int fmt_mt_fetch_text_all(fmt_ctx* c, uint16_t placeholder, uint64_t* offsets, u
   return FMT_OK;
 }
 
+int fmt_mt_fetch_prop_runs_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_prop_run* out, uint64_t cap) {
+  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
+    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_prop_runs_all: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_prop_runs_all");
+  FMT_HIP(c, hipSetDevice(c->device));
+  const uint32_t nd = c->mtDocs;
+  // sumViews is shared with the summaries, the digest and the text read: uploaded again ahead of the
+  // launches of each call (runsViews lives in the ctx: the copy is asynchronous). The views carry the
+  // huge documents' own classes (docViews: SumView::cls).
+  auto uploadViews = [&]() -> hipError_t {
+    docViews(c, c->runsViews);
+    const hipError_t e = c->sumViews.reserve(nd);
+    return e != hipSuccess ? e
+                           : hipMemcpyAsync(c->sumViews.p, c->runsViews.data(), nd * sizeof(fmt_kernels::SumView),
+                                            hipMemcpyHostToDevice, c->stream);
+  };
+  if (!c->runsSized) {
+    // the work items and the class spans from the headers, the classes, pass 1, the stitch on the host
+    std::vector<fmt_mt_doc_result> hdr(nd);
+    FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+    fmt_plan::planTextTiles(hdr.data(), nd, fmt_plan::kTextTileLeaves, c->runsPlan);
+    const size_t ni = c->runsPlan.items.size();
+    if (ni > 0xFFFFFFFFull) return setErr(c, FMT_E_CAPACITY, "fmt_mt_fetch_prop_runs_all: more than 2^32 - 1 work items");
+    docViews(c, c->runsViews);
+    c->runsClsOffs.assign(nd + 1ull, 0);
+    for (uint32_t d = 0; d < nd; d++)
+      c->runsClsOffs[d + 1] = c->runsClsOffs[d] + (hdr[d].status == FMT_OK && c->runsViews[d].cls == nullptr ? hdr[d].n_props : 0u);
+    FMT_HIP(c, c->runsItems.reserve(ni));
+    FMT_HIP(c, c->runsClsOff.reserve(nd + 1ull));
+    FMT_HIP(c, c->runsCls.reserve(c->runsClsOffs[nd]));
+    FMT_HIP(c, c->runsTiles.reserve(ni));
+    FMT_HIP(c, c->runsBases.reserve(ni));
+    FMT_HIP(c, c->runsHostTiles.reserve(ni));
+    FMT_HIP(c, c->runsHostBases.reserve(ni));
+    c->runsOffs.assign(nd + 1ull, 0);
+    if (ni) {
+      FMT_HIP(c, uploadViews());
+      FMT_HIP(c, hipMemcpyAsync(c->runsItems.p, c->runsPlan.items.data(), ni * sizeof(fmt_plan::TextItem),
+                                hipMemcpyHostToDevice, c->stream));
+      FMT_HIP(c, hipMemcpyAsync(c->runsClsOff.p, c->runsClsOffs.data(), (nd + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                c->stream));
+      if (c->runsClsOffs[nd])
+        FMT_HIP(c, fmt_kernels::launchRunClasses(c->mtHdr.p, c->sumViews.p, nd, c->runsClsOff.p, c->runsCls.p, c->numCUs, c->stream));
+      FMT_HIP(c, fmt_kernels::launchRunTileReport(c->mtHdr.p, c->sumViews.p, c->runsItems.p, static_cast<uint32_t>(ni),
+                                                  c->runsClsOff.p, c->runsCls.p, c->runsTiles.p, c->numCUs, c->stream));
+      FMT_HIP(c, hipMemcpyAsync(c->runsHostTiles.p, c->runsTiles.p, ni * sizeof(fmt_plan::RunTile), hipMemcpyDeviceToHost, c->stream));
+      FMT_HIP(c, hipStreamSynchronize(c->stream));
+      fmt_plan::stitchRuns(c->runsPlan, c->runsHostTiles.p, c->runsOffs.data(), c->runsHostBases.p);
+      FMT_HIP(c, hipMemcpyAsync(c->runsBases.p, c->runsHostBases.p, ni * sizeof(fmt_plan::RunTileBase), hipMemcpyHostToDevice, c->stream));
+      FMT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing of this call is in flight past here)
+    }
+    c->runsSized = true;
+  }
+  std::memcpy(offsets, c->runsOffs.data(), (nd + 1ull) * sizeof(uint64_t));
+  const uint64_t total = c->runsOffs[nd];
+  if (out == nullptr) return FMT_OK;
+  if (cap < total) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_prop_runs_all: cap below the number of runs");
+  if (total == 0) return FMT_OK;
+  // pass 2: every item's runs to its base in the packed runs, then one staged copy of exactly those
+  FMT_HIP(c, c->runsPacked.reserve(total));
+  FMT_HIP(c, uploadViews());
+  FMT_HIP(c, fmt_kernels::launchRunEmit(c->mtHdr.p, c->sumViews.p, c->runsItems.p, static_cast<uint32_t>(c->runsPlan.items.size()),
+                                        c->runsClsOff.p, c->runsCls.p, c->runsBases.p, total, c->runsPacked.p, c->numCUs,
+                                        c->stream));
+  FMT_HIP(c, stagedCopy(c, out, c->runsPacked.p, total * sizeof(fmt_mt_prop_run), false));
+  return FMT_OK;
+}
+
+int fmt_mt_fetch_props_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_propset* out, uint64_t cap) {
+  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
+    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_props_all: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_props_all");
+  FMT_HIP(c, hipSetDevice(c->device));
+  const uint32_t nd = c->mtDocs;
+  std::vector<fmt_mt_doc_result> hdr(nd);
+  FMT_HIP(c, hipMemcpy(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost));
+  offsets[0] = 0;
+  for (uint32_t d = 0; d < nd; d++) offsets[d + 1] = offsets[d] + (hdr[d].status == FMT_OK ? hdr[d].n_props : 0u);
+  if (out == nullptr) return FMT_OK;
+  if (cap < offsets[nd]) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_props_all: cap below the number of prop-set records");
+  if (offsets[nd] == 0) return FMT_OK;
+  // each document's records packed on the device (gatherSpansKernel), then one staged copy of exactly those
+  constexpr uint32_t kPW = sizeof(fmt_mt_propset) / 4;
+  std::vector<fmt_kernels::SumView> views;
+  docViews(c, views);
+  std::vector<fmt_kernels::GatherSpan> sp;
+  sp.reserve(nd);
+  for (uint32_t d = 0; d < nd; d++)
+    if (offsets[d + 1] > offsets[d])
+      sp.push_back({reinterpret_cast<const uint32_t*>(views[d].props), offsets[d] * kPW,
+                    static_cast<uint32_t>(offsets[d + 1] - offsets[d]) * kPW, 0u});
+  FMT_HIP(c, c->spans.reserve(sp.size()));
+  FMT_HIP(c, c->packed.reserve(offsets[nd] * kPW));
+  FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
+                            c->stream));
+  FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
+  FMT_HIP(c, stagedCopy(c, out, c->packed.p, offsets[nd] * sizeof(fmt_mt_propset), false));
+  return FMT_OK;
+}
+
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
@@ -2677,6 +2803,31 @@ int fmt_internal_text_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32
     w.insert(w.end(), offs.begin(), offs.end());
     w.insert(w.end(), base.begin(), base.end() - 1);
   }
+  *out = w.data();
+  *nWords = w.size();
+  return FMT_OK;
+}
+
+// Test hook (not part of fmt_runs.h): fmt_mt_fetch_prop_runs_all's host half (runs_plan.h stitchRuns) over
+// host headers and one pass-1 report per work item of planTextTiles(hdrs, tileLeaves) (5 words each: units,
+// heads, tail, first, last), no device needed. Words: the number of items; the offsets (n_docs + 1); per
+// item its run base, position base, open start and flags. Valid until the calling thread's next call.
+int fmt_internal_runs_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_t tileLeaves, const uint32_t* tiles,
+                           uint64_t nTiles, const uint64_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint64_t> w;
+  if ((nDocs && hdrs == nullptr) || out == nullptr || nWords == nullptr) return FMT_E_USAGE;
+  fmt_plan::TextPlan P;
+  fmt_plan::planTextTiles(hdrs, nDocs, tileLeaves, P);
+  if (nTiles != P.items.size() || (nTiles && tiles == nullptr)) return FMT_E_USAGE;
+  static_assert(sizeof(fmt_plan::RunTile) == 5 * sizeof(uint32_t), "RunTile is five words");
+  std::vector<fmt_plan::RunTile> t(P.items.size() + 1);
+  if (nTiles) std::memcpy(t.data(), tiles, nTiles * sizeof(fmt_plan::RunTile));
+  std::vector<uint64_t> offs(nDocs + 1ull);
+  std::vector<fmt_plan::RunTileBase> base(P.items.size() + 1);
+  fmt_plan::stitchRuns(P, t.data(), offs.data(), base.data());
+  w.assign(1, P.items.size());
+  w.insert(w.end(), offs.begin(), offs.end());
+  for (size_t k = 0; k < P.items.size(); k++) w.insert(w.end(), {base[k].runBase, base[k].posBase, base[k].openStart, base[k].flags});
   *out = w.data();
   *nWords = w.size();
   return FMT_OK;

@@ -1340,6 +1340,64 @@ class MergeTreeReplay {
 		}
 		return out;
 	}
+	/**
+	 * Every document as rich text in one device pass (fmt_mt_fetch_prop_runs_all + fmt_mt_fetch_props_all,
+	 * fmt_runs.h, and texts(placeholder)): per document an array of [text, properties or null, isMarker],
+	 * one entry per maximal run of visible text of equal properties; a Marker is an entry of its own whose
+	 * text is the placeholder ("" without one). No per-document fetch, except numbers(doc) for a
+	 * document whose sets hold computed values. A document that failed gives undefined.
+	 */
+	formatted(placeholder) {
+		const ph = typeof placeholder === "string" ? placeholder.charCodeAt(0) || 0 : placeholder || 0;
+		const n = this.batch.nDocs;
+		const texts = this.texts(ph);
+		const r = native().fetchPropRunsAll(this.engine.ctx, n);
+		const at = (v, d) => v.getUint32(8 * d, true) + v.getUint32(8 * d + 4, true) * 4294967296;
+		const ro = new DataView(r.runOffsets), po = new DataView(r.propOffsets);
+		const rv = new DataView(r.runs), pv = new DataView(r.props);
+		const out = new Array(n);
+		for (let d = 0; d < n; d++) {
+			if (this.header(d).status !== 0) {
+				out[d] = undefined;
+				continue;
+			}
+			const base = at(po, d), nProps = at(po, d + 1) - base;
+			const vals = docValues(this.batch, d);
+			let nums;
+			const sets = new Map();
+			const setOf = (p) => {
+				if (p === 0xffff || p >= nProps) return null;
+				if (sets.has(p)) return sets.get(p);
+				const cnt = pv.getUint32((base + p) * PROPSET_BYTES, true);
+				const wide = cnt === FMT_MT_PROPS_CONT || p + Math.floor((cnt - 1) / PROPS_MAX) >= nProps ? 0 : cnt;
+				const obj = {};
+				for (let k = 0; k < wide; k++) {
+					const kv = pv.getUint32((base + p + Math.floor(k / PROPS_MAX)) * PROPSET_BYTES + 4 + 4 * (k % PROPS_MAX), true);
+					const val = kv & 0xffff;
+					if (val === 0) continue;
+					if (val >= FMT_MT_VALUE_COMPUTED && this.batch.adjusts) {
+						if (nums === undefined) nums = this.numbers(d);
+						obj[this.batch.keys[kv >>> 16]] = nums[val - FMT_MT_VALUE_COMPUTED];
+					} else {
+						obj[this.batch.keys[kv >>> 16]] = JSON.parse(vals[val]);
+					}
+				}
+				sets.set(p, obj);
+				return obj;
+			};
+			const doc = [];
+			let t = 0;
+			for (let k = at(ro, d); k < at(ro, d + 1); k++) {
+				const o = 16 * k;
+				const marker = (rv.getUint16(o + 14, true) & 1) !== 0;
+				const units = marker ? (ph ? 1 : 0) : rv.getUint32(o + 4, true);
+				doc.push([texts[d].slice(t, t + units), setOf(rv.getUint16(o + 12, true)), marker]);
+				t += units;
+			}
+			out[d] = doc;
+		}
+		return out;
+	}
 	getLength(doc) {
 		return this.header(doc).visibleLength;
 	}

@@ -26,6 +26,7 @@
 //   fetchRmClientsHi(ctx, doc, nLeaves) -> BigUint64Array            fmt_mt_fetch_rm_clients_hi (ids 64..127)
 //   fetchRmClientsHi2(ctx, doc, nLeaves) -> BigUint64Array           fmt_mt_fetch_rm_clients_hi2 (ids 128..253)
 //   fetchTextAll(ctx, nDocs, placeholder) -> {offsets, text}         fmt_mt_fetch_text_all (fmt_text.h)
+//   fetchPropRunsAll(ctx, nDocs) -> {runOffsets, runs, propOffsets, props}  fmt_mt_fetch_prop_runs_all + fmt_mt_fetch_props_all (fmt_runs.h)
 //   fetchRegen(ctx, doc) -> {ops: ArrayBuffer, text: Uint16Array}     fmt_mt_fetch_regen (f4 reconnects)
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
 //   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
@@ -53,6 +54,7 @@
 #include "fmt.h"
 #include "fmt_map_summary.h"
 #include "fmt_map_tiered.h"
+#include "fmt_runs.h"
 #include "fmt_text.h"
 
 namespace {
@@ -1245,6 +1247,53 @@ napi_value FetchTextAll(napi_env env, napi_callback_info info) {
   return o;
 }
 
+// fetchPropRunsAll(ctx, nDocs) -> {runOffsets, runs, propOffsets, props}: four ArrayBuffers, every document's
+// property runs (16-byte fmt_mt_prop_run records) and prop-set tables (36-byte fmt_mt_propset records) packed in
+// document order, each with its nDocs + 1 uint64 offsets (fmt_mt_fetch_prop_runs_all, fmt_mt_fetch_props_all;
+// nDocs = the loaded batch's document count)
+napi_value FetchPropRunsAll(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  uint32_t nd;
+  if (argc < 2 || !get_ctx(env, argv[0], &c) || !get_u32(env, argv[1], "nDocs", &nd)) return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "fetchPropRunsAll: a replay is running on this context");
+    return nullptr;
+  }
+  using Fn = int (*)(fmt_ctx*, uint64_t*, void*, uint64_t);
+  const Fn fetch[2] = {reinterpret_cast<Fn>(libfmt_symbol("fmt_mt_fetch_prop_runs_all")),
+                       reinterpret_cast<Fn>(libfmt_symbol("fmt_mt_fetch_props_all"))};
+  if (fetch[0] == nullptr || fetch[1] == nullptr) {
+    throw_fmt(env, FMT_E_UNSUPPORTED, "fetchPropRunsAll: the loaded libfmt has no fmt_mt_fetch_prop_runs_all");
+    return nullptr;
+  }
+  const size_t rec[2] = {sizeof(fmt_mt_prop_run), sizeof(fmt_mt_propset)};
+  const char* const names[2][2] = {{"runOffsets", "runs"}, {"propOffsets", "props"}};
+  napi_value o;
+  CHECK_NAPI(env, napi_create_object(env, &o));
+  for (int k = 0; k < 2; k++) {
+    void *po = nullptr, *pr = nullptr;
+    napi_value ob = nullptr, rb = nullptr;
+    CHECK_NAPI(env, napi_create_arraybuffer(env, (size_t(nd) + 1) * sizeof(uint64_t), &po, &ob));
+    uint64_t* offs = static_cast<uint64_t*>(po);
+    int rc = fetch[k](c->ctx, offs, nullptr, 0);
+    if (rc == FMT_OK) {
+      const uint64_t total = offs[nd];
+      CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(total) * rec[k], &pr, &rb));
+      if (total) rc = fetch[k](c->ctx, offs, pr, total);
+    }
+    if (rc != FMT_OK) {
+      throw_fmt(env, rc, fmt_last_error(c->ctx));
+      return nullptr;
+    }
+    CHECK_NAPI(env, napi_set_named_property(env, o, names[k][0], ob));
+    CHECK_NAPI(env, napi_set_named_property(env, o, names[k][1], rb));
+  }
+  return o;
+}
+
 napi_value FetchRegen(napi_env env, napi_callback_info info) {
   size_t argc = 2;
   napi_value argv[2];
@@ -1335,6 +1384,8 @@ napi_value Init(napi_env env, napi_value exports) {
       // clients: not enumerable for the same reason
       {"fetchTextAll", nullptr, FetchTextAll, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fetchRmClientsHi2", nullptr, FetchRmClientsHi2, nullptr, nullptr, nullptr, napi_default, nullptr},
+      // fmt_runs.h's bulk property runs, the same way
+      {"fetchPropRunsAll", nullptr, FetchPropRunsAll, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof fns / sizeof fns[0], fns);
   napi_value sizes, v;

@@ -62,6 +62,10 @@ assert V1_SEG_DTYPE.itemsize == 32
 V1_MARKER, V1_SOLO, V1_REMOVED = 1, 2, 4  # SumV1Seg.flags
 
 CATCHUP_DTYPE = np.dtype([("op", "<u4"), ("pos1", "<i4"), ("pos2", "<i4"), ("type", "<u4")])
+# include/fmt_runs.h fmt_mt_prop_run
+PROP_RUN_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4"), ("first_leaf", "<u4"), ("props", "<u2"), ("flags", "<u2")])
+assert PROP_RUN_DTYPE.itemsize == 16
+RUN_MARKER = 1  # fmt_runs.h FMT_MT_RUN_MARKER
 
 from .streams import (NO_MARKER, RELPOS_DTYPE, SNAPSHOT_DOC_DTYPE, SNAPSHOT_INFO_DTYPE, SNAPSHOT_SEG_DTYPE,  # noqa: E402
                       STAMP_DTYPE)  # (include/fmt.h layouts)
@@ -274,6 +278,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_fetch_text_all", [P, ctypes.c_uint16, P, P, U64]),
                            ("fmt_mt_text_tile_leaves", []),
                            ("fmt_internal_text_plan", [P, U32, U32, P, ctypes.POINTER(P), ctypes.POINTER(U64)]),
+                           ("fmt_mt_fetch_prop_runs_all", [P, P, P, U64]),
+                           ("fmt_mt_fetch_props_all", [P, P, P, U64]),
+                           ("fmt_internal_runs_plan", [P, U32, U32, P, U64, ctypes.POINTER(P), ctypes.POINTER(U64)]),
                            ("fmt_internal_map_summary_arrays", [P, P, P, P, U64]),
                            ("fmt_internal_map_summary_host_only", [P, ctypes.c_int])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
@@ -304,6 +311,8 @@ EXPORTED_SYMBOLS_MAP_TIERED = ["fmt_map_run_sparse_tiered"]
 EXPORTED_SYMBOLS_MAP_SUMMARY = ["fmt_map_summarize", "fmt_map_summary_blobs", "fmt_map_summary_blob"]
 # include/fmt_text.h (bulk getText)
 EXPORTED_SYMBOLS_TEXT = ["fmt_mt_fetch_text_all", "fmt_mt_text_tile_leaves"]
+# include/fmt_runs.h (bulk property runs)
+EXPORTED_SYMBOLS_RUNS = ["fmt_mt_fetch_prop_runs_all", "fmt_mt_fetch_props_all"]
 MAP_SUMMARY_CONTENT = 0xFFFFFFFF    # tag of an ordered entry that stays in the header's "content"
 MAP_SUMMARY_DEVICE_MAX = 2048       # live entries per document the device tier orders (csrc/map_sum_plan.h)
 
@@ -460,6 +469,14 @@ def mt_plan(batch, struct=None) -> MtPlanResult:
     return r
 
 
+MT_VALUE_COMPUTED = 0x8000  # fmt.h FMT_MT_VALUE_COMPUTED: value ids at or above it index the document's numbers
+
+
+def _computed(x):
+    x = float(x)
+    return int(x) if x.is_integer() else x
+
+
 class TextPlanResult:
     """What text_plan read back (csrc/text_plan.h): `items` ((n, 3): doc, first leaf, leaves), `doc_first`
     (n_docs + 1: each document's first item) and, when tile units were given, `offsets` (n_docs + 1) and
@@ -505,6 +522,37 @@ def text_plan(headers, tile_leaves: int = 0, tile_units=None) -> TextPlanResult:
         r.tile_base = w[at : at + ni]
         at += ni
     assert at == len(w)
+    return r
+
+
+RUN_END_MARKER, RUN_END_HAS = 1 << 16, 1 << 17  # csrc/runs_plan.h RunTile.first / last
+RUN_CONTINUES, RUN_CLOSES = 1, 2                # csrc/runs_plan.h RunTileBase.flags
+RUN_TILE_DTYPE = np.dtype([("units", "<u4"), ("heads", "<u4"), ("tail", "<u4"), ("first", "<u4"), ("last", "<u4")])
+
+
+class RunsPlanResult:
+    """What runs_plan read back (csrc/runs_plan.h stitchRuns): `offsets` (n_docs + 1: each document's first
+    run) and per work item `run_base`, `pos_base`, `open_start`, `flags` (RUN_CONTINUES | RUN_CLOSES)."""
+
+
+def runs_plan(headers, tiles, tile_leaves: int = 0) -> RunsPlanResult:
+    """fmt_internal_runs_plan: fmt_mt_fetch_prop_runs_all's host half over result headers (DOC_RESULT_DTYPE)
+    and one pass-1 report (RUN_TILE_DTYPE) per work item of text_plan(headers, tile_leaves), no device
+    needed."""
+    hdr = np.ascontiguousarray(headers, dtype=DOC_RESULT_DTYPE)
+    t = np.ascontiguousarray(tiles, dtype=RUN_TILE_DTYPE)
+    P = ctypes.c_void_p
+    out, n = P(), ctypes.c_uint64()
+    rc = lib().fmt_internal_runs_plan(_ptr(hdr) if len(hdr) else None, len(hdr), tile_leaves, _ptr(t) if len(t) else None,
+                                      len(t), ctypes.byref(out), ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_runs_plan")
+    w = np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy()
+    ni = int(w[0])
+    r = RunsPlanResult()
+    r.offsets = w[1 : 2 + len(hdr)]
+    per = w[2 + len(hdr) :].reshape(ni, 4)
+    r.run_base, r.pos_base, r.open_start, r.flags = (per[:, k].copy() for k in range(4))
     return r
 
 
@@ -805,6 +853,65 @@ class Engine:
         offs, units = self.mt_texts(placeholder)
         raw = units.tobytes()
         return [raw[2 * int(a) : 2 * int(b)].decode("utf-16-le", "surrogatepass") for a, b in zip(offs[:-1], offs[1:])]
+
+    # ---- bulk property runs of the last merge-tree run (include/fmt_runs.h)
+    def _bulk(self, fn, dtype):
+        offs = np.zeros(self._mt_docs + 1, dtype=np.uint64)
+        self._check(fn(self.h, _ptr(offs), None, 0))
+        total = int(offs[-1])
+        out = np.zeros(max(total, 1), dtype=dtype)
+        self._check(fn(self.h, _ptr(offs), _ptr(out), total))
+        return offs, out[:total]
+
+    def mt_prop_runs(self):
+        """fmt_mt_fetch_prop_runs_all: every document's property runs from the local perspective in one
+        device pass: (offsets uint64[n_docs + 1], runs PROP_RUN_DTYPE[total]), document d's runs at
+        runs[offsets[d]:offsets[d + 1]] (none for a document that failed)."""
+        return self._bulk(self.L.fmt_mt_fetch_prop_runs_all, PROP_RUN_DTYPE)
+
+    def mt_props_all(self):
+        """fmt_mt_fetch_props_all: every document's prop-set table in one copy: (offsets uint64[n_docs + 1],
+        records PROPSET_DTYPE[total]); a run's `props` names a first record of its document's span."""
+        return self._bulk(self.L.fmt_mt_fetch_props_all, PROPSET_DTYPE)
+
+    def mt_formatted(self, keys, values, placeholder: int = 0) -> list:
+        """Every document as rich text: per document a list of (text, props dict or None, is_marker), one
+        entry per property run, from mt_prop_runs, mt_props_all and mt_texts(placeholder); no per-document
+        fetch except mt_numbers for a document whose sets hold computed values. A Marker's text is the
+        placeholder, or "" without one. A document that failed gives None."""
+        import json
+
+        status = self.mt_headers(raise_on_failed_docs=False)["status"]
+        roffs, runs = self.mt_prop_runs()
+        poffs, props = self.mt_props_all()
+        toffs, units = self.mt_texts(placeholder)
+        raw = units.tobytes()
+        out = []
+        for d in range(self._mt_docs):
+            if int(status[d]) != FMT_OK:
+                out.append(None)
+                continue
+            table = props[int(poffs[d]) : int(poffs[d + 1])]
+            numbers = None
+            dicts = {}
+            at = int(toffs[d])
+            doc = []
+            for r in runs[int(roffs[d]) : int(roffs[d + 1])]:
+                pid, marker = int(r["props"]), bool(int(r["flags"]) & RUN_MARKER)
+                if pid != 0xFFFF and pid not in dicts:
+                    kv = propset_entries(table, pid)
+                    if numbers is None and any((e & 0xFFFF) >= MT_VALUE_COMPUTED for e in kv):
+                        numbers = self.mt_numbers(d)
+                    dicts[pid] = {keys[e >> 16]: (_computed(numbers[(e & 0xFFFF) - MT_VALUE_COMPUTED])
+                                                  if (e & 0xFFFF) >= MT_VALUE_COMPUTED else json.loads(values[e & 0xFFFF]))
+                                  for e in kv if e & 0xFFFF}  # (value id 0: null, the key is absent)
+                n = (1 if placeholder else 0) if marker else int(r["len"])
+                doc.append((raw[2 * at : 2 * (at + n)].decode("utf-16-le", "surrogatepass"),
+                            None if pid == 0xFFFF else dicts[pid], marker))
+                at += n
+            assert at == int(toffs[d + 1]), f"document {d}: runs cover {at - int(toffs[d])} units of {int(toffs[d + 1] - toffs[d])}"
+            out.append(doc)
+        return out
 
     def mt_digests(self) -> np.ndarray:
         """fmt_mt_state_digest: every document's 64-bit content digest."""

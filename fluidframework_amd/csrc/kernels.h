@@ -4,9 +4,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fmt.h"
+#include "../../include/fmt_pos.h"
 #include "../../include/fmt_runs.h"
 #include "map_plan.h"
 #include "mt_bind.h"
+#include "pos_plan.h"
 #include "runs_plan.h"
 #include "text_plan.h"
 
@@ -152,6 +154,15 @@ hipError_t launchRunEmit(const fmt_mt_doc_result* hdrs, const SumView* views, co
                          uint32_t nItems, const unsigned long long* clsOff, const uint16_t* clsBuf,
                          const fmt_plan::RunTileBase* bases, uint64_t nRuns, fmt_mt_prop_run* runs, int numCUs,
                          hipStream_t stream);
+
+// Bulk position queries (pos.hip; include/fmt_pos.h; views, tile lookup and the records decided on the host:
+// pos_plan.h). One wave per item. launchPosTileUnits writes per (view, tile) item its units in the view and in
+// the local view; launchPosResolve writes the hit of each of the nDev queries at its `out` index, every
+// index below nQueries, and nothing for a query whose tile does not hold its position.
+hipError_t launchPosTileUnits(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::PosItem* items,
+                              uint32_t nItems, fmt_plan::PosTileUnits* tileUnits, int numCUs, hipStream_t stream);
+hipError_t launchPosResolve(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::PosDevQuery* queries,
+                            uint64_t nDev, uint64_t nQueries, fmt_mt_pos_hit* out, int numCUs, hipStream_t stream);
 
 struct MtCaps {
   uint32_t leaves, chars, props;

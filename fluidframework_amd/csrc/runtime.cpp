@@ -17,6 +17,7 @@
 #include "../../include/fmt.h"
 #include "../../include/fmt_map_summary.h"
 #include "../../include/fmt_map_tiered.h"
+#include "../../include/fmt_pos.h"
 #include "../../include/fmt_runs.h"
 #include "../../include/fmt_text.h"
 #include "../../include/fmt_v1.h"
@@ -309,6 +310,16 @@ struct fmt_ctx {
   PinnedBuf<fmt_plan::RunTile> runsHostTiles;
   PinnedBuf<fmt_plan::RunTileBase> runsHostBases;
   bool runsSized = false;                       // classes, pass 1 and the stitch hold since the last run
+  // bulk position queries (fmt_mt_query_positions, pos.hip): the plan of the call (pos_plan.h), its items,
+  // the units per item, the queries that go to the device, the records. Its own buffers and nothing cached:
+  // no other read sees them, and it reads none of theirs.
+  fmt_plan::PosPlan posPlan;
+  std::vector<fmt_kernels::SumView> posViews;
+  DevBuf<fmt_plan::PosItem> posItems;
+  DevBuf<fmt_plan::PosTileUnits> posUnits;
+  DevBuf<fmt_plan::PosDevQuery> posQueries;
+  DevBuf<fmt_mt_pos_hit> posHits;
+  PinnedBuf<fmt_plan::PosTileUnits> posHostUnits;
 };
 
 namespace {
@@ -535,6 +546,10 @@ void fmt_close(fmt_ctx* c) {
   c->runsTiles.release();
   c->runsBases.release();
   c->runsPacked.release();
+  c->posItems.release();
+  c->posUnits.release();
+  c->posQueries.release();
+  c->posHits.release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -2627,6 +2642,62 @@ int fmt_mt_fetch_props_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_propset* out, u
   return FMT_OK;
 }
 
+int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_pos_query* q, uint64_t nQueries,
+                           fmt_mt_pos_hit* out) {
+  if (c == nullptr || !c->mtLoaded || qOffsets == nullptr || (nQueries && (q == nullptr || out == nullptr)))
+    return setErr(c, FMT_E_USAGE, "fmt_mt_query_positions: bad arguments");
+  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_query_positions");
+  const uint32_t nd = c->mtDocs;
+  if (!fmt_plan::posOffsetsValid(qOffsets, nd, nQueries))
+    return setErr(c, FMT_E_USAGE, "fmt_mt_query_positions: q_offsets must ascend from 0 to n_queries");
+  if (nQueries == 0) return FMT_OK;
+  FMT_HIP(c, hipSetDevice(c->device));
+  // the statuses the headers decide, the views and their (view, tile) items
+  std::vector<fmt_mt_doc_result> hdr(nd);
+  FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  fmt_plan::PosPlan& P = c->posPlan;
+  const int rc = fmt_plan::planPosViews(hdr.data(), nd, c->mtPlan.obliterates, fmt_plan::kTextTileLeaves, qOffsets, q, nQueries, out, P);
+  if (rc != FMT_OK) return setErr(c, rc, "fmt_mt_query_positions: more than 2^32 - 1 views or work items");
+  // sumViews is shared with the summaries, the digest, the text and the runs reads: uploaded again ahead of
+  // each launch (posViews lives in the ctx: the copy is asynchronous)
+  auto uploadViews = [&]() -> hipError_t {
+    docViews(c, c->posViews);
+    const hipError_t e = c->sumViews.reserve(nd);
+    return e != hipSuccess ? e
+                           : hipMemcpyAsync(c->sumViews.p, c->posViews.data(), nd * sizeof(fmt_kernels::SumView),
+                                            hipMemcpyHostToDevice, c->stream);
+  };
+  // pass 1: every item's units in its view and in the local view; the prefixes and the tile lookup on the host
+  const size_t ni = P.items.size();
+  FMT_HIP(c, c->posHostUnits.reserve(ni));
+  if (ni) {
+    FMT_HIP(c, c->posItems.reserve(ni));
+    FMT_HIP(c, c->posUnits.reserve(ni));
+    FMT_HIP(c, uploadViews());
+    FMT_HIP(c, hipMemcpyAsync(c->posItems.p, P.items.data(), ni * sizeof(fmt_plan::PosItem), hipMemcpyHostToDevice, c->stream));
+    FMT_HIP(c, fmt_kernels::launchPosTileUnits(c->mtHdr.p, c->sumViews.p, c->posItems.p, static_cast<uint32_t>(ni), c->posUnits.p,
+                                               c->numCUs, c->stream));
+    FMT_HIP(c, hipMemcpyAsync(c->posHostUnits.p, c->posUnits.p, ni * sizeof(fmt_plan::PosTileUnits), hipMemcpyDeviceToHost,
+                              c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  fmt_plan::resolvePosQueries(P, hdr.data(), c->posHostUnits.p, q, nQueries, out);
+  const size_t nDev = P.dev.size();
+  if (nDev == 0) return FMT_OK;
+  // pass 2: the records as the host left them go up, every device query's lane writes its own, and one
+  // staged copy brings them all back (stagedCopy waits for the stream first)
+  FMT_HIP(c, c->posQueries.reserve(nDev));
+  FMT_HIP(c, c->posHits.reserve(nQueries));
+  FMT_HIP(c, stagedCopy(c, c->posHits.p, out, nQueries * sizeof(fmt_mt_pos_hit), true));
+  FMT_HIP(c, stagedCopy(c, c->posQueries.p, P.dev.data(), nDev * sizeof(fmt_plan::PosDevQuery), true));
+  FMT_HIP(c, uploadViews());
+  FMT_HIP(c, fmt_kernels::launchPosResolve(c->mtHdr.p, c->sumViews.p, c->posQueries.p, nDev, nQueries, c->posHits.p, c->numCUs,
+                                           c->stream));
+  FMT_HIP(c, stagedCopy(c, out, c->posHits.p, nQueries * sizeof(fmt_mt_pos_hit), false));
+  return FMT_OK;
+}
+
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
     return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
@@ -2828,6 +2899,44 @@ int fmt_internal_runs_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32
   w.assign(1, P.items.size());
   w.insert(w.end(), offs.begin(), offs.end());
   for (size_t k = 0; k < P.items.size(); k++) w.insert(w.end(), {base[k].runBase, base[k].posBase, base[k].openStart, base[k].flags});
+  *out = w.data();
+  *nWords = w.size();
+  return FMT_OK;
+}
+
+// Test hook (not part of fmt_pos.h): fmt_mt_query_positions' host half (pos_plan.h) over host headers, no
+// device needed. tile_leaves 0: the kernels' tile. hits[n_queries] receives the records as the host leaves
+// them. Words: the number of views; the views (doc, ref_seq, client, first item; signed values
+// sign-extended); the number of items; the items (doc, first leaf, leaves, view); and, when tile_units (two
+// per item: view, local; so from a second call) is given, the number of device queries and the queries (doc,
+// first leaf, leaves, pos, ref_seq, client, view base, local base, out). Returns planPosViews' status. Valid
+// until the calling thread's next call.
+int fmt_internal_pos_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_t obliterates, uint32_t tileLeaves,
+                          const uint64_t* qOffsets, const fmt_mt_pos_query* q, uint64_t nQueries, const uint64_t* tileUnits,
+                          uint64_t nTileUnits, fmt_mt_pos_hit* hits, const uint64_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint64_t> w;
+  if ((nDocs && hdrs == nullptr) || qOffsets == nullptr || (nQueries && (q == nullptr || hits == nullptr)) || out == nullptr ||
+      nWords == nullptr)
+    return FMT_E_USAGE;
+  fmt_plan::PosPlan P;
+  const int rc = fmt_plan::planPosViews(hdrs, nDocs, obliterates != 0, tileLeaves, qOffsets, q, nQueries, hits, P);
+  if (rc != FMT_OK) return rc;
+  auto sx = [](int32_t x) { return static_cast<uint64_t>(static_cast<int64_t>(x)); };
+  w.assign(1, P.views.size());
+  for (const fmt_plan::PosView& v : P.views) w.insert(w.end(), {uint64_t{v.doc}, sx(v.refSeq), sx(v.client), v.firstItem});
+  w.push_back(P.items.size());
+  for (const fmt_plan::PosItem& it : P.items) w.insert(w.end(), {it.doc, it.firstLeaf, it.nLeaves, it.view});
+  if (tileUnits != nullptr) {
+    if (nTileUnits != P.items.size()) return FMT_E_USAGE;
+    static_assert(sizeof(fmt_plan::PosTileUnits) == 2 * sizeof(uint64_t), "PosTileUnits is two words");
+    std::vector<fmt_plan::PosTileUnits> u(P.items.size() + 1);
+    std::memcpy(u.data(), tileUnits, P.items.size() * sizeof(fmt_plan::PosTileUnits));
+    fmt_plan::resolvePosQueries(P, hdrs, u.data(), q, nQueries, hits);
+    w.push_back(P.dev.size());
+    for (const fmt_plan::PosDevQuery& d : P.dev)
+      w.insert(w.end(), {uint64_t{d.doc}, uint64_t{d.firstLeaf}, uint64_t{d.nLeaves}, uint64_t{d.pos}, sx(d.refSeq), sx(d.client),
+                         uint64_t{d.viewBase}, uint64_t{d.localBase}, d.out});
+  }
   *out = w.data();
   *nWords = w.size();
   return FMT_OK;

@@ -54,6 +54,7 @@ const MT_OP_BYTES = 32, MAP_OP_BYTES = 16, LEAF_BYTES = 32, DOC_RESULT_BYTES = 4
 const CATCHUP_BYTES = 16, SNAPSHOT_DOC_BYTES = 32;
 const NO_PROPS = 0xffffffff;
 const PROPS_MAX = 8, FMT_MT_PROPS_CONT = 0xffffffff; // fmt.h: entries per prop-set record; n of a continuation record
+const POS_VIEW_LOCAL = 0x7fffffff; // fmt_pos.h FMT_MT_VIEW_LOCAL: a position query's refSeq naming the local view
 
 let addon = null;
 /** The native addon; throws if it was not built (there is no JavaScript fallback engine). */
@@ -1398,6 +1399,45 @@ class MergeTreeReplay {
 		}
 		return out;
 	}
+	/**
+	 * Position queries over every document in one device pass (fmt_mt_query_positions, fmt_pos.h): the
+	 * reference's getContainingSegment / getPropertiesAtPosition / resolveRemoteClientPosition in bulk.
+	 * queries: an array of {doc, pos, refSeq, client} in any order; refSeq absent (or POS_VIEW_LOCAL): the
+	 * local view, else the view of short client id `client` at refSeq. Returns one object per query, in the
+	 * queries' order: {status, leaf, offset, leafStart, leafLen, localPos, props (prop-set id, 0xffff none),
+	 * unit, marker, end, hiddenLocally}. A query that cannot be answered carries its own status (fmt_pos.h);
+	 * the call throws only for misuse.
+	 */
+	positions(queries) {
+		const n = this.batch.nDocs;
+		const order = queries.map((_, i) => i);
+		for (const q of queries) {
+			if (!Number.isInteger(q.doc) || q.doc < 0 || q.doc >= n) throw new RangeError(`positions: document ${q.doc} outside the batch`);
+		}
+		order.sort((a, b) => queries[a].doc - queries[b].doc || a - b);
+		const offs = new BigUint64Array(n + 1);
+		const qv = new DataView(new ArrayBuffer(16 * queries.length));
+		order.forEach((i, k) => {
+			const q = queries[i];
+			offs[q.doc + 1]++;
+			qv.setUint32(16 * k, q.pos, true);
+			qv.setInt32(16 * k + 4, q.refSeq === undefined || q.refSeq === null ? POS_VIEW_LOCAL : q.refSeq, true);
+			qv.setInt32(16 * k + 8, q.client || 0, true);
+		});
+		for (let d = 0; d < n; d++) offs[d + 1] += offs[d];
+		const hv = new DataView(native().queryPositions(this.engine.ctx, n, offs.buffer, qv.buffer));
+		const out = new Array(queries.length);
+		order.forEach((i, k) => {
+			const o = 32 * k, flags = hv.getUint32(o + 28, true);
+			out[i] = {
+				status: hv.getInt32(o + 24, true), leaf: hv.getUint32(o, true), offset: hv.getUint32(o + 4, true),
+				leafStart: hv.getUint32(o + 8, true), leafLen: hv.getUint32(o + 12, true), localPos: hv.getUint32(o + 16, true),
+				props: hv.getUint16(o + 20, true), unit: hv.getUint16(o + 22, true), marker: (flags & 1) !== 0, end: (flags & 2) !== 0,
+				hiddenLocally: (flags & 4) !== 0,
+			};
+		});
+		return out;
+	}
 	getLength(doc) {
 		return this.header(doc).visibleLength;
 	}
@@ -1571,5 +1611,5 @@ module.exports = {
 	summary,
 	constants: { MT_INSERT, MT_REMOVE, MT_ANNOTATE, MT_GROUP, MAP_SET, MAP_DELETE, MAP_CLEAR,
 		MAP_VALUE_UNDEFINED, MAP_ABSENT, FMT_MT_F_GROUP_CONT, FMT_MT_F_CATCHUP, NOT_REMOVED,
-		FMT_MT_F_LOCAL, FMT_MT_F_ACK, FMT_MT_F_ROLLBACK, FMT_MT_F_REGEN, FMT_MT_LOCAL_SEQ_BASE: 0x40000000 },
+		FMT_MT_F_LOCAL, FMT_MT_F_ACK, FMT_MT_F_ROLLBACK, FMT_MT_F_REGEN, FMT_MT_LOCAL_SEQ_BASE: 0x40000000, POS_VIEW_LOCAL },
 };

@@ -27,6 +27,7 @@
 //   fetchRmClientsHi2(ctx, doc, nLeaves) -> BigUint64Array           fmt_mt_fetch_rm_clients_hi2 (ids 128..253)
 //   fetchTextAll(ctx, nDocs, placeholder) -> {offsets, text}         fmt_mt_fetch_text_all (fmt_text.h)
 //   fetchPropRunsAll(ctx, nDocs) -> {runOffsets, runs, propOffsets, props}  fmt_mt_fetch_prop_runs_all + fmt_mt_fetch_props_all (fmt_runs.h)
+//   queryPositions(ctx, nDocs, qOffsets, queries) -> hits              fmt_mt_query_positions (fmt_pos.h)
 //   fetchRegen(ctx, doc) -> {ops: ArrayBuffer, text: Uint16Array}     fmt_mt_fetch_regen (f4 reconnects)
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
 //   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
@@ -54,6 +55,7 @@
 #include "fmt.h"
 #include "fmt_map_summary.h"
 #include "fmt_map_tiered.h"
+#include "fmt_pos.h"
 #include "fmt_runs.h"
 #include "fmt_text.h"
 
@@ -1294,6 +1296,50 @@ napi_value FetchPropRunsAll(napi_env env, napi_callback_info info) {
   return o;
 }
 
+// queryPositions(ctx, nDocs, qOffsets, queries) -> ArrayBuffer of 32-byte fmt_mt_pos_hit records, one per query
+// (fmt_mt_query_positions, fmt_pos.h). qOffsets: ArrayBuffer of nDocs + 1 uint64, ascending from 0 to the number
+// of queries; queries: ArrayBuffer of 16-byte fmt_mt_pos_query records packed per document (nDocs = the loaded
+// batch's document count).
+napi_value QueryPositions(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  uint32_t nd;
+  if (argc < 4 || !get_ctx(env, argv[0], &c) || !get_u32(env, argv[1], "nDocs", &nd)) return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "queryPositions: a replay is running on this context");
+    return nullptr;
+  }
+  void *po = nullptr, *pq = nullptr;
+  size_t no = 0, nq = 0;
+  if (napi_get_arraybuffer_info(env, argv[2], &po, &no) != napi_ok || napi_get_arraybuffer_info(env, argv[3], &pq, &nq) != napi_ok) {
+    throw_fmt(env, FMT_E_USAGE, "queryPositions: qOffsets and queries are ArrayBuffers");
+    return nullptr;
+  }
+  if (no != (size_t(nd) + 1) * sizeof(uint64_t) || nq % sizeof(fmt_mt_pos_query) != 0) {
+    throw_fmt(env, FMT_E_USAGE, "queryPositions: qOffsets holds nDocs + 1 uint64, queries 16-byte records");
+    return nullptr;
+  }
+  using Fn = int (*)(fmt_ctx*, const uint64_t*, const fmt_mt_pos_query*, uint64_t, fmt_mt_pos_hit*);
+  const Fn query = reinterpret_cast<Fn>(libfmt_symbol("fmt_mt_query_positions"));
+  if (query == nullptr) {
+    throw_fmt(env, FMT_E_UNSUPPORTED, "queryPositions: the loaded libfmt has no fmt_mt_query_positions");
+    return nullptr;
+  }
+  const uint64_t n = nq / sizeof(fmt_mt_pos_query);
+  void* ph = nullptr;
+  napi_value hb = nullptr;
+  CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(n) * sizeof(fmt_mt_pos_hit), &ph, &hb));
+  const int rc = query(c->ctx, static_cast<const uint64_t*>(po), static_cast<const fmt_mt_pos_query*>(pq), n,
+                       static_cast<fmt_mt_pos_hit*>(ph));
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  return hb;
+}
+
 napi_value FetchRegen(napi_env env, napi_callback_info info) {
   size_t argc = 2;
   napi_value argv[2];
@@ -1386,6 +1432,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fetchRmClientsHi2", nullptr, FetchRmClientsHi2, nullptr, nullptr, nullptr, napi_default, nullptr},
       // fmt_runs.h's bulk property runs, the same way
       {"fetchPropRunsAll", nullptr, FetchPropRunsAll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      // fmt_pos.h's bulk position queries, the same way
+      {"queryPositions", nullptr, QueryPositions, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof fns / sizeof fns[0], fns);
   napi_value sizes, v;

@@ -66,6 +66,13 @@ CATCHUP_DTYPE = np.dtype([("op", "<u4"), ("pos1", "<i4"), ("pos2", "<i4"), ("typ
 PROP_RUN_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4"), ("first_leaf", "<u4"), ("props", "<u2"), ("flags", "<u2")])
 assert PROP_RUN_DTYPE.itemsize == 16
 RUN_MARKER = 1  # fmt_runs.h FMT_MT_RUN_MARKER
+# include/fmt_pos.h fmt_mt_pos_query / fmt_mt_pos_hit
+POS_QUERY_DTYPE = np.dtype([("pos", "<u4"), ("ref_seq", "<i4"), ("client", "<i4"), ("pad", "<u4")])
+POS_HIT_DTYPE = np.dtype([("leaf", "<u4"), ("offset", "<u4"), ("leaf_start", "<u4"), ("leaf_len", "<u4"), ("local_pos", "<u4"),
+                          ("props", "<u2"), ("unit", "<u2"), ("status", "<i4"), ("flags", "<u4")])
+assert POS_QUERY_DTYPE.itemsize == 16 and POS_HIT_DTYPE.itemsize == 32
+VIEW_LOCAL = 0x7FFFFFFF  # fmt_pos.h FMT_MT_VIEW_LOCAL
+POS_F_MARKER, POS_F_END, POS_F_HIDDEN_LOCALLY = 1, 2, 4  # fmt_pos.h FMT_MT_POS_F_*
 
 from .streams import (NO_MARKER, RELPOS_DTYPE, SNAPSHOT_DOC_DTYPE, SNAPSHOT_INFO_DTYPE, SNAPSHOT_SEG_DTYPE,  # noqa: E402
                       STAMP_DTYPE)  # (include/fmt.h layouts)
@@ -281,6 +288,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_fetch_prop_runs_all", [P, P, P, U64]),
                            ("fmt_mt_fetch_props_all", [P, P, P, U64]),
                            ("fmt_internal_runs_plan", [P, U32, U32, P, U64, ctypes.POINTER(P), ctypes.POINTER(U64)]),
+                           ("fmt_mt_query_positions", [P, P, P, U64, P]),
+                           ("fmt_internal_pos_plan", [P, U32, U32, U32, P, P, U64, P, U64, P, ctypes.POINTER(P),
+                                                      ctypes.POINTER(U64)]),
                            ("fmt_internal_map_summary_arrays", [P, P, P, P, U64]),
                            ("fmt_internal_map_summary_host_only", [P, ctypes.c_int])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
@@ -313,6 +323,8 @@ EXPORTED_SYMBOLS_MAP_SUMMARY = ["fmt_map_summarize", "fmt_map_summary_blobs", "f
 EXPORTED_SYMBOLS_TEXT = ["fmt_mt_fetch_text_all", "fmt_mt_text_tile_leaves"]
 # include/fmt_runs.h (bulk property runs)
 EXPORTED_SYMBOLS_RUNS = ["fmt_mt_fetch_prop_runs_all", "fmt_mt_fetch_props_all"]
+# include/fmt_pos.h (bulk position queries)
+EXPORTED_SYMBOLS_POS = ["fmt_mt_query_positions"]
 MAP_SUMMARY_CONTENT = 0xFFFFFFFF    # tag of an ordered entry that stays in the header's "content"
 MAP_SUMMARY_DEVICE_MAX = 2048       # live entries per document the device tier orders (csrc/map_sum_plan.h)
 
@@ -553,6 +565,52 @@ def runs_plan(headers, tiles, tile_leaves: int = 0) -> RunsPlanResult:
     r.offsets = w[1 : 2 + len(hdr)]
     per = w[2 + len(hdr) :].reshape(ni, 4)
     r.run_base, r.pos_base, r.open_start, r.flags = (per[:, k].copy() for k in range(4))
+    return r
+
+
+class PosPlanResult:
+    """What pos_plan read back (csrc/pos_plan.h): `hits` (POS_HIT_DTYPE, one per query, as the host leaves
+    them: statuses, ends, and FMT_E_DATA where the device is to write), `views` ((n, 4) int64: doc, ref_seq,
+    client, first item), `items` ((n, 4): doc, first leaf, leaves, view) and, when tile units were given,
+    `dev` ((n, 9) int64: doc, first leaf, leaves, pos within the tile, ref_seq, client, view base, local
+    base, index of the query's record)."""
+
+
+def pos_plan(headers, queries, q_offsets, tile_units=None, obliterates: bool = False, tile_leaves: int = 0) -> PosPlanResult:
+    """fmt_internal_pos_plan: fmt_mt_query_positions' host half over result headers (DOC_RESULT_DTYPE), no
+    device needed. tile_leaves 0: the kernels' tile. tile_units ((n_items, 2): units in the view, units in
+    the local view): also the tile lookup of every query. Raises EngineError(FMT_E_USAGE) for malformed
+    q_offsets."""
+    hdr = np.ascontiguousarray(headers, dtype=DOC_RESULT_DTYPE)
+    q = np.ascontiguousarray(queries, dtype=POS_QUERY_DTYPE)
+    offs = np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    if len(offs) != len(hdr) + 1:
+        raise EngineError(FMT_E_USAGE, f"{len(offs)} q_offsets for {len(hdr)} documents")
+    units = None if tile_units is None else np.ascontiguousarray(tile_units, dtype=np.uint64).reshape(-1, 2)
+    hits = np.zeros(max(len(q), 1), dtype=POS_HIT_DTYPE)
+    P = ctypes.c_void_p
+    out, n = P(), ctypes.c_uint64()
+    rc = lib().fmt_internal_pos_plan(_ptr(hdr) if len(hdr) else None, len(hdr), 1 if obliterates else 0, tile_leaves, _ptr(offs),
+                                     _ptr(q) if len(q) else None, len(q),
+                                     None if units is None else _ptr(units if len(units) else np.zeros(2, np.uint64)),
+                                     0 if units is None else len(units), _ptr(hits), ctypes.byref(out), ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_pos_plan")
+    w = np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy().view(np.int64)
+    r = PosPlanResult()
+    r.hits = hits[: len(q)]
+    nv = int(w[0])
+    r.views = w[1 : 1 + 4 * nv].reshape(nv, 4)
+    at = 1 + 4 * nv
+    ni = int(w[at])
+    r.items = w[at + 1 : at + 1 + 4 * ni].reshape(ni, 4)
+    at += 1 + 4 * ni
+    r.dev = None
+    if units is not None:
+        ndev = int(w[at])
+        r.dev = w[at + 1 : at + 1 + 9 * ndev].reshape(ndev, 9)
+        at += 1 + 9 * ndev
+    assert at == len(w)
     return r
 
 
@@ -911,6 +969,40 @@ class Engine:
                 at += n
             assert at == int(toffs[d + 1]), f"document {d}: runs cover {at - int(toffs[d])} units of {int(toffs[d + 1] - toffs[d])}"
             out.append(doc)
+        return out
+
+    # ---- bulk position queries of the last merge-tree run (include/fmt_pos.h)
+    def mt_positions(self, queries, q_offsets) -> np.ndarray:
+        """fmt_mt_query_positions: every query of every document answered in one device pass. queries:
+        POS_QUERY_DTYPE (pos, ref_seq, client; ref_seq VIEW_LOCAL: the local view), packed per document;
+        q_offsets: n_docs + 1 offsets, ascending from 0 to len(queries). Returns POS_HIT_DTYPE[len(queries)],
+        hit i answering query i; a query that could not be answered carries its own status, the call raises
+        only for misuse (bad offsets, no completed run)."""
+        q = np.ascontiguousarray(queries, dtype=POS_QUERY_DTYPE)
+        offs = np.ascontiguousarray(q_offsets, dtype=np.uint64)
+        if len(offs) != self._mt_docs + 1:
+            raise EngineError(FMT_E_USAGE, f"mt_positions: {len(offs)} q_offsets for {self._mt_docs} documents")
+        out = np.zeros(max(len(q), 1), dtype=POS_HIT_DTYPE)
+        self._check(self.L.fmt_mt_query_positions(self.h, _ptr(offs), _ptr(q) if len(q) else None, len(q), _ptr(out)))
+        return out[: len(q)]
+
+    def mt_positions_local(self, doc_ids, positions) -> np.ndarray:
+        """mt_positions for local-view queries given as parallel arrays in any order: hit i answers
+        (doc_ids[i], positions[i])."""
+        docs = np.asarray(doc_ids, dtype=np.int64)
+        pos = np.asarray(positions, dtype=np.uint32)
+        if docs.shape != pos.shape or docs.ndim != 1:
+            raise EngineError(FMT_E_USAGE, "mt_positions_local: doc_ids and positions must be parallel 1-d arrays")
+        if len(docs) and (int(docs.min()) < 0 or int(docs.max()) >= self._mt_docs):
+            raise EngineError(FMT_E_USAGE, "mt_positions_local: a document id outside the loaded batch")
+        order = np.argsort(docs, kind="stable")
+        q = np.zeros(len(docs), dtype=POS_QUERY_DTYPE)
+        q["pos"] = pos[order]
+        q["ref_seq"] = VIEW_LOCAL
+        offs = np.zeros(self._mt_docs + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(np.bincount(docs, minlength=self._mt_docs), dtype=np.uint64)
+        out = np.zeros(len(docs), dtype=POS_HIT_DTYPE)
+        out[order] = self.mt_positions(q, offs)
         return out
 
     def mt_digests(self) -> np.ndarray:

@@ -14,10 +14,11 @@
 
 #include "../../include/fmt.h"
 #include "kernels.h"
+#include "sum_wave.h"
 
 namespace fmt_kernels {
 
-constexpr int kDigWaves = 4;
+constexpr int kDigWaves = kSumWaves;  // (waveGrid sizes the grid)
 
 __device__ __forceinline__ uint64_t digMix(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -87,10 +88,7 @@ __global__ __launch_bounds__(64 * kDigWaves) void stateDigestKernel(const fmt_mt
 
 hipError_t launchStateDigest(const fmt_mt_doc_result* hdrs, const SumView* views, uint32_t nDocs, uint64_t* out,
                              int numCUs, hipStream_t stream) {
-  const uint32_t wanted = (nDocs + kDigWaves - 1) / kDigWaves;
-  const uint32_t cap = static_cast<uint32_t>(numCUs) * 8u;
-  const uint32_t grid = wanted < cap ? (wanted > 0 ? wanted : 1) : cap;
-  hipLaunchKernelGGL(stateDigestKernel, dim3(grid), dim3(64 * kDigWaves), 0, stream, hdrs, views, nDocs, out);
+  hipLaunchKernelGGL(stateDigestKernel, dim3(waveGrid(nDocs, numCUs)), dim3(64 * kDigWaves), 0, stream, hdrs, views, nDocs, out);
   return hipGetLastError();
 }
 

@@ -35,11 +35,6 @@ using fmt_plan::PosDevQuery;
 using fmt_plan::PosItem;
 using fmt_plan::PosTileUnits;
 
-__device__ __forceinline__ uint32_t posItemLeaves(const fmt_mt_doc_result& h, uint32_t firstLeaf, uint32_t nLeaves) {
-  if (h.status != FMT_OK || firstLeaf >= h.n_leaves) return 0;
-  return nLeaves < h.n_leaves - firstLeaf ? nLeaves : h.n_leaves - firstLeaf;
-}
-
 __device__ __forceinline__ uint32_t posUnitsOf(const fmt_mt_leaf& L) { return (L.pad & FMT_MT_LEAF_MARKER) != 0 ? 1u : L.len; }
 
 __device__ __forceinline__ bool posVisibleLocal(const fmt_mt_leaf& L) { return L.rm_seq == FMT_NOT_REMOVED; }
@@ -52,27 +47,16 @@ __device__ __forceinline__ bool posVisible(const fmt_mt_leaf& L, int32_t refSeq,
   return inserted && !removed;
 }
 
-// Inclusive prefix of x over the wave's lanes.
-__device__ __forceinline__ uint32_t posScan(uint32_t x, int lane) {
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = static_cast<uint32_t>(__shfl_up(static_cast<int>(x), o));
-    if (lane >= o) x += t;
-  }
-  return x;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64 * kSumWaves) void posTileUnitsKernel(const fmt_mt_doc_result* __restrict__ hdrs,
                                                                const SumView* __restrict__ views,
                                                                const PosItem* __restrict__ items, uint32_t nItems,
                                                                PosTileUnits* __restrict__ tileUnits) {
-  const uint32_t wave = threadIdx.x >> 6;
   const uint32_t lane = threadIdx.x & 63;
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nItems;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nItems; k += waveItemStride()) {
     const PosItem it = items[k];
-    const uint32_t n = posItemLeaves(hdrs[it.doc], it.firstLeaf, it.nLeaves);
+    const uint32_t n = waveItemLeaves(hdrs[it.doc], it.firstLeaf, it.nLeaves);
     const fmt_mt_leaf* leaves = views[it.doc].leaves + it.firstLeaf;
     unsigned long long inView = 0, inLocal = 0;
     for (uint32_t b = 0; b < n; b += 64) {
@@ -96,13 +80,11 @@ __global__ __launch_bounds__(64 * kSumWaves) void posResolveKernel(const fmt_mt_
                                                              const SumView* __restrict__ views,
                                                              const PosDevQuery* __restrict__ queries, uint64_t nDev,
                                                              uint64_t nQueries, fmt_mt_pos_hit* __restrict__ out) {
-  const uint32_t wave = threadIdx.x >> 6;
   const int lane = static_cast<int>(threadIdx.x & 63);
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nDev;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nDev; k += waveItemStride()) {
     const PosDevQuery Q = queries[k];
     const fmt_mt_doc_result h = hdrs[Q.doc];
-    const uint32_t n = posItemLeaves(h, Q.firstLeaf, Q.nLeaves);
+    const uint32_t n = waveItemLeaves(h, Q.firstLeaf, Q.nLeaves);
     const SumView V = views[Q.doc];
     const fmt_mt_leaf* leaves = V.leaves + Q.firstLeaf;
     uint32_t before = 0, beforeLocal = 0;  // units of the chunks walked so far
@@ -116,7 +98,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void posResolveKernel(const fmt_mt_
         u = posVisible(L, Q.refSeq, Q.client) ? units : 0u;
         ul = posVisibleLocal(L) ? units : 0u;
       }
-      const uint32_t incl = posScan(u, lane), inclLocal = posScan(ul, lane);
+      const uint32_t incl = waveScan(u, lane), inclLocal = waveScan(ul, lane);
       const uint32_t start = before + incl - u;  // (sums of one tile of one document: below 2^32)
       const bool hit = u != 0 && start <= Q.pos && Q.pos - start < u;
       if (hit && Q.out < nQueries) {
@@ -142,22 +124,16 @@ __global__ __launch_bounds__(64 * kSumWaves) void posResolveKernel(const fmt_mt_
   }
 }
 
-static uint32_t posGrid(uint64_t nWaves, int numCUs) {
-  const uint64_t wanted = (nWaves + kSumWaves - 1) / kSumWaves;
-  const uint64_t cap = static_cast<uint64_t>(numCUs) * 8u;
-  return static_cast<uint32_t>(wanted < cap ? (wanted > 0 ? wanted : 1) : cap);
-}
-
 hipError_t launchPosTileUnits(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::PosItem* items,
                               uint32_t nItems, fmt_plan::PosTileUnits* tileUnits, int numCUs, hipStream_t stream) {
-  hipLaunchKernelGGL(posTileUnitsKernel, dim3(posGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, items,
+  hipLaunchKernelGGL(posTileUnitsKernel, dim3(waveGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, items,
                      nItems, tileUnits);
   return hipGetLastError();
 }
 
 hipError_t launchPosResolve(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::PosDevQuery* queries,
                             uint64_t nDev, uint64_t nQueries, fmt_mt_pos_hit* out, int numCUs, hipStream_t stream) {
-  hipLaunchKernelGGL(posResolveKernel, dim3(posGrid(nDev, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, queries,
+  hipLaunchKernelGGL(posResolveKernel, dim3(waveGrid(nDev, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, queries,
                      nDev, nQueries, out);
   return hipGetLastError();
 }

@@ -55,7 +55,6 @@ struct PosView {
 constexpr uint32_t kPosNoView = 0xFFFFFFFFu;
 
 struct PosPlan {
-  TextPlan tiles;
   std::vector<PosView> views;
   std::vector<PosItem> items;
   std::vector<uint32_t> qView;  // per query: its view, or kPosNoView (its record holds its status already)
@@ -85,14 +84,13 @@ inline bool posOffsetsValid(const uint64_t* qOffsets, uint32_t nDocs, uint64_t n
   return true;
 }
 
-// Zeroes out[0 .. nQueries) and writes the statuses known from the headers; fills P.tiles, P.views, P.items
-// and P.qView. Returns FMT_E_USAGE for malformed offsets (nothing written), FMT_E_CAPACITY for more than
+// Zeroes out[0 .. nQueries) and writes the statuses known from the headers; fills P.views, P.items and P.qView
+// over `tiles`, the text read's plan of these headers (text_plan.h planTextTiles). Returns FMT_E_USAGE for malformed offsets (nothing written), FMT_E_CAPACITY for more than
 // 2^32 - 1 views or items.
-inline int planPosViews(const fmt_mt_doc_result* hdrs, uint32_t nDocs, bool obliterates, uint32_t tileLeaves,
+inline int planPosViews(const fmt_mt_doc_result* hdrs, uint32_t nDocs, bool obliterates, const TextPlan& tiles,
                         const uint64_t* qOffsets, const fmt_mt_pos_query* q, uint64_t nQueries, fmt_mt_pos_hit* out,
                         PosPlan& P) {
   if (!posOffsetsValid(qOffsets, nDocs, nQueries)) return FMT_E_USAGE;
-  planTextTiles(hdrs, nDocs, tileLeaves, P.tiles);
   P.views.clear();
   P.items.clear();
   P.dev.clear();
@@ -117,8 +115,8 @@ inline int planPosViews(const fmt_mt_doc_result* hdrs, uint32_t nDocs, bool obli
       const int32_t client = static_cast<int32_t>(static_cast<uint32_t>(k));
       const uint32_t v = static_cast<uint32_t>(P.views.size());
       P.views.push_back(PosView{d, refSeq, client, 0u, P.items.size()});
-      for (uint64_t t = P.tiles.docFirst[d]; t < P.tiles.docFirst[d + 1]; t++) {
-        const TextItem& it = P.tiles.items[t];
+      for (uint64_t t = tiles.docFirst[d]; t < tiles.docFirst[d + 1]; t++) {
+        const TextItem& it = tiles.items[t];
         P.items.push_back(PosItem{d, it.firstLeaf, it.nLeaves, v, refSeq, client, {0u, 0u}});
       }
     }
@@ -132,9 +130,9 @@ inline int planPosViews(const fmt_mt_doc_result* hdrs, uint32_t nDocs, bool obli
   return FMT_OK;
 }
 
-// From units[P.items.size()]: every query's final record (end, past end) or its PosDevQuery in P.dev, in
+// From units[P.items.size()] and the tiles planPosViews took: every query's final record (end, past end) or its PosDevQuery in P.dev, in
 // query order, with its record pre-filled FMT_E_DATA.
-inline void resolvePosQueries(PosPlan& P, const fmt_mt_doc_result* hdrs, const PosTileUnits* units,
+inline void resolvePosQueries(PosPlan& P, const TextPlan& tiles, const fmt_mt_doc_result* hdrs, const PosTileUnits* units,
                               const fmt_mt_pos_query* q, uint64_t nQueries, fmt_mt_pos_hit* out) {
   const size_t ni = P.items.size();
   P.viewBase.assign(ni + 1, 0);
@@ -142,7 +140,7 @@ inline void resolvePosQueries(PosPlan& P, const fmt_mt_doc_result* hdrs, const P
   std::vector<uint64_t> viewLen(P.views.size()), localLen(P.views.size());
   for (size_t v = 0; v < P.views.size(); v++) {
     const PosView& V = P.views[v];
-    const uint64_t nt = P.tiles.docFirst[V.doc + 1] - P.tiles.docFirst[V.doc];
+    const uint64_t nt = tiles.docFirst[V.doc + 1] - tiles.docFirst[V.doc];
     uint64_t at = 0, lat = 0;
     for (uint64_t k = V.firstItem; k < V.firstItem + nt; k++) {
       P.viewBase[k] = at;
@@ -173,7 +171,7 @@ inline void resolvePosQueries(PosPlan& P, const fmt_mt_doc_result* hdrs, const P
       continue;
     }
     // the last tile whose base is at or below pos: the next base is above it, so the tile holds the position
-    const uint64_t nt = P.tiles.docFirst[V.doc + 1] - P.tiles.docFirst[V.doc];
+    const uint64_t nt = tiles.docFirst[V.doc + 1] - tiles.docFirst[V.doc];
     const uint64_t* first = P.viewBase.data() + V.firstItem;
     const uint64_t k = V.firstItem + static_cast<uint64_t>(std::upper_bound(first, first + nt, pos) - first) - 1;
     const PosItem& it = P.items[k];

@@ -42,11 +42,6 @@ using fmt_plan::TextItem;
 
 constexpr uint32_t kKeyMarker = fmt_plan::kRunEndMarker;
 
-__device__ __forceinline__ uint32_t runItemLeaves(const fmt_mt_doc_result& h, const TextItem& it) {
-  if (h.status != FMT_OK || it.firstLeaf >= h.n_leaves) return 0;
-  return it.nLeaves < h.n_leaves - it.firstLeaf ? it.nLeaves : h.n_leaves - it.firstLeaf;
-}
-
 // A chunk of 64 leaves as both passes see it: per lane whether its leaf counts, its units, its class with
 // the marker flag (key), and whether it is a head given the carry of the chunks before.
 struct RunChunk {
@@ -78,25 +73,14 @@ __device__ __forceinline__ RunChunk runChunk(const fmt_mt_leaf* leaves, uint32_t
   return c;
 }
 
-// Inclusive prefix of x over the wave's lanes.
-__device__ __forceinline__ uint32_t runScan(uint32_t x, int lane) {
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = static_cast<uint32_t>(__shfl_up(static_cast<int>(x), o));
-    if (lane >= o) x += t;
-  }
-  return x;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64 * kSumWaves) void runClassKernel(const fmt_mt_doc_result* __restrict__ hdrs,
                                                            const SumView* __restrict__ views, uint32_t nDocs,
                                                            const unsigned long long* __restrict__ clsOff,
                                                            uint16_t* __restrict__ clsBuf) {
-  const uint32_t wave = threadIdx.x >> 6;
   const uint32_t lane = threadIdx.x & 63;
-  for (uint64_t d = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; d < nDocs;
-       d += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t d = waveItemFirst(); d < nDocs; d += waveItemStride()) {
     const SumView V = views[d];
     // document d's span, sized by the host from its header: n_props entries, none for a failed or a huge document
     const uint32_t np = static_cast<uint32_t>(clsOff[d + 1] - clsOff[d]);
@@ -122,13 +106,11 @@ __global__ __launch_bounds__(64 * kSumWaves) void runTileReportKernel(const fmt_
                                                                 const unsigned long long* __restrict__ clsOff,
                                                                 const uint16_t* __restrict__ clsBuf,
                                                                 RunTile* __restrict__ tiles) {
-  const uint32_t wave = threadIdx.x >> 6;
   const int lane = static_cast<int>(threadIdx.x & 63);
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nItems;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nItems; k += waveItemStride()) {
     const TextItem it = items[k];
     const fmt_mt_doc_result h = hdrs[it.doc];
-    const uint32_t n = runItemLeaves(h, it);
+    const uint32_t n = waveItemLeaves(h, it.firstLeaf, it.nLeaves);
     const SumView V = views[it.doc];
     const fmt_mt_leaf* leaves = V.leaves + it.firstLeaf;
     const uint16_t* cls = clsBuf + clsOff[it.doc];
@@ -138,7 +120,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void runTileReportKernel(const fmt_
     uint32_t carryKey = 0;
     for (uint32_t b = 0; b < n; b += 64) {
       const RunChunk c = runChunk(leaves, b + static_cast<uint32_t>(lane), n, lane, V, cls, np, carryHas, carryKey);
-      const uint32_t incl = runScan(c.units, lane);
+      const uint32_t incl = waveScan(c.units, lane);
       const uint32_t chunkUnits = sumUni(static_cast<uint32_t>(__shfl(static_cast<int>(incl), 63)));
       const uint64_t heads = __ballot(c.head);
       const int lastHead = heads != 0 ? 63 - __clzll(static_cast<long long>(heads)) : 0;
@@ -166,13 +148,11 @@ __global__ __launch_bounds__(64 * kSumWaves) void runEmitKernel(const fmt_mt_doc
                                                           const uint16_t* __restrict__ clsBuf,
                                                           const RunTileBase* __restrict__ bases, uint64_t nRuns,
                                                           fmt_mt_prop_run* __restrict__ runs) {
-  const uint32_t wave = threadIdx.x >> 6;
   const int lane = static_cast<int>(threadIdx.x & 63);
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nItems;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nItems; k += waveItemStride()) {
     const TextItem it = items[k];
     const fmt_mt_doc_result h = hdrs[it.doc];
-    const uint32_t n = runItemLeaves(h, it);
+    const uint32_t n = waveItemLeaves(h, it.firstLeaf, it.nLeaves);
     const SumView V = views[it.doc];
     const fmt_mt_leaf* leaves = V.leaves + it.firstLeaf;
     const uint16_t* cls = clsBuf + clsOff[it.doc];
@@ -187,7 +167,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void runEmitKernel(const fmt_mt_doc
     for (uint32_t b = 0; b < n; b += 64) {
       const uint32_t i = b + static_cast<uint32_t>(lane);
       const RunChunk c = runChunk(leaves, i, n, lane, V, cls, np, carryHas, carryKey);
-      const uint32_t incl = runScan(c.units, lane);
+      const uint32_t incl = waveScan(c.units, lane);
       const uint32_t chunkUnits = sumUni(static_cast<uint32_t>(__shfl(static_cast<int>(incl), 63)));
       const uint32_t start = pos + incl - c.units;
       // the tile's first visible leaf is no head when it continues the run open at the tile's start
@@ -226,15 +206,9 @@ __global__ __launch_bounds__(64 * kSumWaves) void runEmitKernel(const fmt_mt_doc
   }
 }
 
-static uint32_t runGrid(uint64_t nWaves, int numCUs) {
-  const uint64_t wanted = (nWaves + kSumWaves - 1) / kSumWaves;
-  const uint64_t cap = static_cast<uint64_t>(numCUs) * 8u;
-  return static_cast<uint32_t>(wanted < cap ? (wanted > 0 ? wanted : 1) : cap);
-}
-
 hipError_t launchRunClasses(const fmt_mt_doc_result* hdrs, const SumView* views, uint32_t nDocs,
                             const unsigned long long* clsOff, uint16_t* clsBuf, int numCUs, hipStream_t stream) {
-  hipLaunchKernelGGL(runClassKernel, dim3(runGrid(nDocs, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, nDocs,
+  hipLaunchKernelGGL(runClassKernel, dim3(waveGrid(nDocs, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, nDocs,
                      clsOff, clsBuf);
   return hipGetLastError();
 }
@@ -242,7 +216,7 @@ hipError_t launchRunClasses(const fmt_mt_doc_result* hdrs, const SumView* views,
 hipError_t launchRunTileReport(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
                                uint32_t nItems, const unsigned long long* clsOff, const uint16_t* clsBuf,
                                fmt_plan::RunTile* tiles, int numCUs, hipStream_t stream) {
-  hipLaunchKernelGGL(runTileReportKernel, dim3(runGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
+  hipLaunchKernelGGL(runTileReportKernel, dim3(waveGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
                      items, nItems, clsOff, clsBuf, tiles);
   return hipGetLastError();
 }
@@ -251,7 +225,7 @@ hipError_t launchRunEmit(const fmt_mt_doc_result* hdrs, const SumView* views, co
                          uint32_t nItems, const unsigned long long* clsOff, const uint16_t* clsBuf,
                          const fmt_plan::RunTileBase* bases, uint64_t nRuns, fmt_mt_prop_run* runs, int numCUs,
                          hipStream_t stream) {
-  hipLaunchKernelGGL(runEmitKernel, dim3(runGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, items,
+  hipLaunchKernelGGL(runEmitKernel, dim3(waveGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views, items,
                      nItems, clsOff, clsBuf, bases, nRuns, runs);
   return hipGetLastError();
 }

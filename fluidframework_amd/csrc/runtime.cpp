@@ -228,8 +228,20 @@ struct fmt_ctx {
   DevBuf<fmt_huge::HugeState> hugeStates2;     // descriptors of the documents a run escalated (uploadHuge)
   DevBuf<fmt_huge::HugeInputs> hugeInputs2;
   DevBuf<fmt_kernels::HugeOut> hugeOuts2;
-  // bulk legacy summaries (fmt_mt_summarize_legacy): device runs / text, host blobs
+  // The read frame: what every bulk read of a run's results starts from. readFrame builds
+  // it for the first read after a run, invalidateReads (fmt_mt_load, fmt_mt_run) makes it stale. The headers
+  // and every document's views (docView) on the host, which the asynchronous copies read, the views in
+  // sumViews, and, from the first reader that walks tiles on (frameTiles), the tile plan at kTextTileLeaves
+  // with its items in tileItems.
+  struct ReadFrame {
+    bool current = false, tiled = false;
+    std::vector<fmt_mt_doc_result> hdr;
+    std::vector<fmt_kernels::SumView> views;
+    fmt_plan::TextPlan tiles;
+  } frame;
   DevBuf<fmt_kernels::SumView> sumViews;
+  DevBuf<fmt_plan::TextItem> tileItems;
+  // bulk legacy summaries (fmt_mt_summarize_legacy): device runs / text, host blobs
   DevBuf<fmt_kernels::SumRun> sumRuns;
   DevBuf<uint16_t> sumText;
   DevBuf<unsigned long long> sumCursors;
@@ -283,25 +295,18 @@ struct fmt_ctx {
   std::vector<std::string> v1Blobs;           // per document: header, then body_0, body_1, ...
   std::vector<std::vector<uint64_t>> v1Ends;  // per document: where each of those blobs ends in v1Blobs[d]
   std::vector<int32_t> v1Status;
-  // bulk getText (fmt_mt_fetch_text_all, text.hip): the work items (text_plan.h), the units per item,
-  // each item's base in the packed text, the packed text. Its own buffers: no summary reads or writes them.
-  fmt_plan::TextPlan textPlan;
-  std::vector<fmt_kernels::SumView> textViews;
+  // bulk getText (fmt_mt_fetch_text_all, text.hip): per work item of the frame's tiles its units and its
+  // base in the packed text, the packed text. Its own buffers: no other read sees them.
   std::vector<uint64_t> textOffs;               // the offsets of the cached pass 1 (n_docs + 1)
-  DevBuf<fmt_plan::TextItem> textItems;
   DevBuf<unsigned long long> textUnits, textBases;
   DevBuf<uint16_t> textPacked;
   PinnedBuf<uint64_t> textHostUnits, textHostBases;
   bool textSized = false;                       // pass 1 and the scan hold for textPlaceholder since the last run
   uint16_t textPlaceholder = 0;
-  // bulk property runs (fmt_mt_fetch_prop_runs_all, runs.hip): the work items again (its own plan and copy:
-  // the text read's may belong to another placeholder's sizing call), each document's span of match
-  // classes, pass 1's report per item, the stitch's bases per item (runs_plan.h), the packed runs.
-  fmt_plan::TextPlan runsPlan;
-  std::vector<fmt_kernels::SumView> runsViews;
+  // bulk property runs (fmt_mt_fetch_prop_runs_all, runs.hip): each document's span of match classes, per work
+  // item of the frame's tiles pass 1's report and the stitch's bases (runs_plan.h), the packed runs.
   std::vector<uint64_t> runsOffs;               // the offsets of the cached sizing pass (n_docs + 1)
   std::vector<uint64_t> runsClsOffs;            // n_docs + 1
-  DevBuf<fmt_plan::TextItem> runsItems;
   DevBuf<unsigned long long> runsClsOff;
   DevBuf<uint16_t> runsCls;
   DevBuf<fmt_plan::RunTile> runsTiles;
@@ -310,11 +315,10 @@ struct fmt_ctx {
   PinnedBuf<fmt_plan::RunTile> runsHostTiles;
   PinnedBuf<fmt_plan::RunTileBase> runsHostBases;
   bool runsSized = false;                       // classes, pass 1 and the stitch hold since the last run
-  // bulk position queries (fmt_mt_query_positions, pos.hip): the plan of the call (pos_plan.h), its items,
-  // the units per item, the queries that go to the device, the records. Its own buffers and nothing cached:
-  // no other read sees them, and it reads none of theirs.
+  // bulk position queries (fmt_mt_query_positions, pos.hip): the plan of the call over the frame's tiles
+  // (pos_plan.h), its items, the units per item, the queries that go to the device, the records. Its own
+  // buffers and nothing cached between calls: no other read sees them.
   fmt_plan::PosPlan posPlan;
-  std::vector<fmt_kernels::SumView> posViews;
   DevBuf<fmt_plan::PosItem> posItems;
   DevBuf<fmt_plan::PosTileUnits> posUnits;
   DevBuf<fmt_plan::PosDevQuery> posQueries;
@@ -419,6 +423,99 @@ hipError_t stagedCopy(fmt_ctx* c, void* dst, const void* src, size_t bytes, bool
   for (hipError_t x : errs)
     if (x != hipSuccess) return x;
   return hipSuccess;
+}
+
+// ---- reads of a merge-tree run's results
+
+// The entry of every such read. `bad`, the function's own message: a null ctx, nothing loaded, or argsOk false
+// (the caller's own arguments, which may look into c only behind `c &&`). Not run since the load: mtNeedsRun
+// under the name `what`, or `bad` again when what is null. Then the device is made current.
+int mtReadEntry(fmt_ctx* c, bool argsOk, const char* what, const std::string& bad) {
+  if (c == nullptr || !c->mtLoaded || !argsOk) return setErr(c, FMT_E_USAGE, bad);
+  if (!c->mtRan) return what != nullptr ? mtNeedsRun(c, what) : setErr(c, FMT_E_USAGE, bad);
+  FMT_HIP(c, hipSetDevice(c->device));
+  return FMT_OK;
+}
+
+// Where document d's converged state lives: the small tier's slabs, a large-tier slab, or a huge
+// document's own buffers.
+fmt_kernels::SumView docView(const fmt_ctx* c, uint32_t d) {
+  const int32_t hs = d < c->mtHugeSlot.size() ? c->mtHugeSlot[d] : -1;
+  if (hs >= 0) {
+    const fmt_kernels::HugeOut& O = c->huge[static_cast<size_t>(hs)].out;
+    return {O.leaves, O.chars, O.props, c->mtPlan.anyAdjust ? O.legacy : nullptr, O.cls, O.leavesHi};
+  }
+  const int32_t slot = d < c->mtBigSlot.size() ? c->mtBigSlot[d] : -1;
+  const fmt_kernels::MtCaps caps = fmt_kernels::mergeTreeCaps(slot >= 0);
+  const size_t at = slot >= 0 ? static_cast<size_t>(slot) : d;
+  return {(slot >= 0 ? c->mtBigLeaves.p : c->mtLeaves.p) + at * caps.leaves,
+          (slot >= 0 ? c->mtBigChars.p : c->mtChars.p) + at * caps.chars,
+          (slot >= 0 ? c->mtBigProps.p : c->mtProps.p) + at * caps.props,
+          c->mtPlan.anyAdjust ? (slot >= 0 ? c->mtBigLegacy.p : c->mtLegacy.p) + at * caps.leaves : nullptr};
+}
+
+// The two places that know which reads cache something between calls: fmt_mt_load and fmt_mt_run.
+void invalidateReads(fmt_ctx* c) {
+  c->frame.current = false;
+  c->frame.tiled = false;
+  c->textSized = false;
+  c->runsSized = false;
+}
+
+// Makes the read frame current and returns it (nullptr: FMT_E_DEVICE, the message set): the headers come down
+// once, every document's view goes up once. Nothing is in flight when it returns, so a later reserve moves
+// nothing a copy still reads.
+const fmt_ctx::ReadFrame* readFrame(fmt_ctx* c) {
+  fmt_ctx::ReadFrame& F = c->frame;
+  if (F.current) return &F;
+  const uint32_t nd = c->mtDocs;
+  F.hdr.resize(nd);
+  F.views.resize(nd);
+  for (uint32_t d = 0; d < nd; d++) F.views[d] = docView(c, d);
+  hipError_t e = c->sumViews.reserve(nd);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(F.hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->sumViews.p, F.views.data(), nd * sizeof(fmt_kernels::SumView), hipMemcpyHostToDevice, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    hipErr(c, e != hipSuccess ? e : e2, "read frame");
+    return nullptr;
+  }
+  F.current = true;
+  return &F;
+}
+
+// The frame with its tile plan and the plan's items on the device, for the readers that walk tiles.
+// `tooMany`: the caller's message for more than 2^32 - 1 items (FMT_E_CAPACITY).
+int frameTiles(fmt_ctx* c, const char* tooMany, const fmt_ctx::ReadFrame** out) {
+  const fmt_ctx::ReadFrame* F = readFrame(c);
+  if (F == nullptr) return FMT_E_DEVICE;
+  *out = F;
+  if (F->tiled) return FMT_OK;
+  fmt_plan::planTextTiles(F->hdr.data(), c->mtDocs, fmt_plan::kTextTileLeaves, c->frame.tiles);
+  const size_t ni = F->tiles.items.size();
+  if (ni > 0xFFFFFFFFull) return setErr(c, FMT_E_CAPACITY, tooMany);
+  FMT_HIP(c, c->tileItems.reserve(ni));
+  FMT_HIP(c, hipMemcpyAsync(c->tileItems.p, F->tiles.items.data(), ni * sizeof(fmt_plan::TextItem), hipMemcpyHostToDevice,
+                            c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  c->frame.tiled = true;
+  return FMT_OK;
+}
+
+// Packs the spans into c->packed on the device (transfer.hip; `words` dwords in all) and, with dst, brings the
+// first `bytes` of the packing to the host in one staged copy, which returns when they are there. Without
+// dst the packing is queued on the stream for the caller's own copies; `sp` lives until the caller's wait.
+int gatherPacked(fmt_ctx* c, const std::vector<fmt_kernels::GatherSpan>& sp, uint64_t words, void* dst, size_t bytes) {
+  if (sp.empty()) return FMT_OK;
+  FMT_HIP(c, c->spans.reserve(sp.size()));
+  FMT_HIP(c, c->packed.reserve(words));
+  FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
+                            c->stream));
+  FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
+  if (dst != nullptr) FMT_HIP(c, stagedCopy(c, dst, c->packed.p, bytes, false));
+  return FMT_OK;
 }
 
 }  // namespace
@@ -536,11 +633,10 @@ void fmt_close(fmt_ctx* c) {
   c->packed.release();
   c->digests.release();
   c->v1Segs.release();
-  c->textItems.release();
+  c->tileItems.release();
   c->textUnits.release();
   c->textBases.release();
   c->textPacked.release();
-  c->runsItems.release();
   c->runsClsOff.release();
   c->runsCls.release();
   c->runsTiles.release();
@@ -1344,8 +1440,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   const fmt_plan::MtPlan& P = c->mtPlan;
   c->mtLoaded = false;  // (from here on the context holds this batch or, after a device error, none)
   c->mtRan = false;
-  c->textSized = false;
-  c->runsSized = false;
+  invalidateReads(c);
   const uint32_t n = b->n_docs;
   const uint32_t nKv = b->props_off ? b->props_off[b->n_props_ops] : 0;
   // host arrays the asynchronous copies below read; the stream is drained before they go, on every way out
@@ -1562,8 +1657,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
 int fmt_mt_run(fmt_ctx* c) {
   if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
   c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
-  c->textSized = false;
-  c->runsSized = false;
+  invalidateReads(c);
   FMT_HIP(c, hipSetDevice(c->device));
   // documents an earlier run of this load escalated into the huge tier start over: their state is
   // released, and only the load-time huge documents (c->mtHugeLoaded) run with the small tiers
@@ -1753,35 +1847,16 @@ int fmt_mt_fetch_headers(fmt_ctx* c, fmt_mt_doc_result* out) {
 
 int fmt_mt_fetch_doc(fmt_ctx* c, uint32_t doc, fmt_mt_leaf* leaves, uint32_t capLeaves, uint16_t* chars,
                      uint32_t capChars, fmt_mt_propset* props, uint32_t capProps) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_doc: bad doc");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_doc");
-  const int32_t hslot = doc < c->mtHugeSlot.size() ? c->mtHugeSlot[doc] : -1;
-  if (hslot >= 0) {  // a huge document: its own output buffers
-    const fmt_kernels::HugeOut& O = c->huge[static_cast<size_t>(hslot)].out;
-    fmt_mt_doc_result h;
-    FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
-    const uint32_t nl = h.n_leaves < capLeaves ? h.n_leaves : capLeaves;
-    const uint32_t nc = h.n_chars < capChars ? h.n_chars : capChars;
-    const uint32_t np = h.n_props < capProps ? h.n_props : capProps;
-    if (leaves && nl) FMT_HIP(c, hipMemcpy(leaves, O.leaves, nl * sizeof(fmt_mt_leaf), hipMemcpyDeviceToHost));
-    if (chars && nc) FMT_HIP(c, hipMemcpy(chars, O.chars, nc * 2ull, hipMemcpyDeviceToHost));
-    if (props && np) FMT_HIP(c, hipMemcpy(props, O.props, np * sizeof(fmt_mt_propset), hipMemcpyDeviceToHost));
-    return FMT_OK;
-  }
-  const int32_t slot = doc < c->mtBigSlot.size() ? c->mtBigSlot[doc] : -1;
-  const fmt_kernels::MtCaps caps = fmt_kernels::mergeTreeCaps(slot >= 0);
-  const size_t at = slot >= 0 ? static_cast<size_t>(slot) : doc;
-  const fmt_mt_leaf* dLeaves = slot >= 0 ? c->mtBigLeaves.p : c->mtLeaves.p;
-  const uint16_t* dChars = slot >= 0 ? c->mtBigChars.p : c->mtChars.p;
-  const fmt_mt_propset* dProps = slot >= 0 ? c->mtBigProps.p : c->mtProps.p;
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs, "fmt_mt_fetch_doc", "fmt_mt_fetch_doc: bad doc")) return rc;
+  const fmt_kernels::SumView V = docView(c, doc);
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t nl = h.n_leaves < capLeaves ? h.n_leaves : capLeaves;
   const uint32_t nc = h.n_chars < capChars ? h.n_chars : capChars;
   const uint32_t np = h.n_props < capProps ? h.n_props : capProps;
-  if (leaves && nl) FMT_HIP(c, hipMemcpy(leaves, dLeaves + at * caps.leaves, nl * sizeof(fmt_mt_leaf), hipMemcpyDeviceToHost));
-  if (chars && nc) FMT_HIP(c, hipMemcpy(chars, dChars + at * caps.chars, nc * 2ull, hipMemcpyDeviceToHost));
-  if (props && np) FMT_HIP(c, hipMemcpy(props, dProps + at * caps.props, np * sizeof(fmt_mt_propset), hipMemcpyDeviceToHost));
+  if (leaves && nl) FMT_HIP(c, hipMemcpy(leaves, V.leaves, nl * sizeof(fmt_mt_leaf), hipMemcpyDeviceToHost));
+  if (chars && nc) FMT_HIP(c, hipMemcpy(chars, V.chars, nc * 2ull, hipMemcpyDeviceToHost));
+  if (props && np) FMT_HIP(c, hipMemcpy(props, V.props, np * sizeof(fmt_mt_propset), hipMemcpyDeviceToHost));
   return FMT_OK;
 }
 
@@ -2071,40 +2146,13 @@ void makeDict(SumDict& D, const char* const* keys, uint32_t nKeys, const char* c
   for (uint32_t k = 0; k < nKeys; k++) D.keyIndex[k] = arrayIndexOfQuoted(D.keys[k]);
 }
 
-// Where each document's converged state lives: the small tier's slabs, a large-tier slab, or a
-// huge document's own buffers.
-void docViews(const fmt_ctx* c, std::vector<fmt_kernels::SumView>& views) {
-  const uint32_t nd = c->mtDocs;
-  views.resize(nd);
-  for (uint32_t d = 0; d < nd; d++) {
-    const int32_t hs = d < c->mtHugeSlot.size() ? c->mtHugeSlot[d] : -1;
-    if (hs >= 0) {
-      const fmt_kernels::HugeOut& O = c->huge[static_cast<size_t>(hs)].out;
-      views[d] = {O.leaves, O.chars, O.props, c->mtPlan.anyAdjust ? O.legacy : nullptr, O.cls, O.leavesHi};
-    } else {
-      const int32_t slot = d < c->mtBigSlot.size() ? c->mtBigSlot[d] : -1;
-      const fmt_kernels::MtCaps caps = fmt_kernels::mergeTreeCaps(slot >= 0);
-      const size_t at = slot >= 0 ? static_cast<size_t>(slot) : d;
-      views[d] = {(slot >= 0 ? c->mtBigLeaves.p : c->mtLeaves.p) + at * caps.leaves,
-                  (slot >= 0 ? c->mtBigChars.p : c->mtChars.p) + at * caps.chars,
-                  (slot >= 0 ? c->mtBigProps.p : c->mtProps.p) + at * caps.props,
-                  c->mtPlan.anyAdjust ? (slot >= 0 ? c->mtBigLegacy.p : c->mtLegacy.p) + at * caps.leaves : nullptr};
-    }
-  }
-}
-
 }  // namespace
 
 int fmt_mt_state_digest(fmt_ctx* c, uint64_t* out) {
-  if (c == nullptr || out == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_state_digest: nothing loaded");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_state_digest");
-  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = mtReadEntry(c, out != nullptr, "fmt_mt_state_digest", "fmt_mt_state_digest: nothing loaded")) return rc;
+  if (readFrame(c) == nullptr) return FMT_E_DEVICE;
   const uint32_t nd = c->mtDocs;
-  std::vector<fmt_kernels::SumView> views;
-  docViews(c, views);
-  FMT_HIP(c, c->sumViews.reserve(nd));
   FMT_HIP(c, c->digests.reserve(nd));
-  FMT_HIP(c, hipMemcpyAsync(c->sumViews.p, views.data(), nd * sizeof(fmt_kernels::SumView), hipMemcpyHostToDevice, c->stream));
   FMT_HIP(c, fmt_kernels::launchStateDigest(c->mtHdr.p, c->sumViews.p, nd, c->digests.p, c->numCUs, c->stream));
   FMT_HIP(c, hipMemcpyAsync(out, c->digests.p, nd * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   FMT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2113,31 +2161,23 @@ int fmt_mt_state_digest(fmt_ctx* c, uint64_t* out) {
 
 int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys, const char* const* values,
                             uint32_t nValues, uint32_t chunk, uint32_t threads, fmt_summary_timing* timing) {
-  if (c == nullptr || !c->mtLoaded || (nKeys && keys == nullptr) || (nValues && values == nullptr))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_summarize_legacy: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_summarize_legacy");
+  if (const int rc = mtReadEntry(c, !(nKeys && keys == nullptr) && !(nValues && values == nullptr), "fmt_mt_summarize_legacy",
+                                 "fmt_mt_summarize_legacy: bad arguments"))
+    return rc;
   using clk = std::chrono::steady_clock;
-  FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
-  std::vector<fmt_mt_doc_result> hdr(nd);
-  FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-  FMT_HIP(c, hipStreamSynchronize(c->stream));
-  // every document's result buffers (small tier, large-tier slab, or huge tier)
-  std::vector<fmt_kernels::SumView> views;
-  docViews(c, views);
-  std::vector<fmt_mt_propset*> propsDev(nd);
+  const fmt_ctx::ReadFrame* F = readFrame(c);
+  if (F == nullptr) return FMT_E_DEVICE;
+  const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
   uint64_t capRuns = 0, capText = 0;
   for (uint32_t d = 0; d < nd; d++) {
-    propsDev[d] = const_cast<fmt_mt_propset*>(views[d].props);
     capRuns += hdr[d].n_leaves;
     capText += hdr[d].n_chars;
   }
-  FMT_HIP(c, c->sumViews.reserve(nd));
   FMT_HIP(c, c->sumRuns.reserve(capRuns));
   FMT_HIP(c, c->sumText.reserve(capText));
   FMT_HIP(c, c->sumCursors.reserve(2));
   FMT_HIP(c, c->sumDocs.reserve(nd));
-  FMT_HIP(c, hipMemcpyAsync(c->sumViews.p, views.data(), nd * sizeof(fmt_kernels::SumView), hipMemcpyHostToDevice, c->stream));
   FMT_HIP(c, hipMemsetAsync(c->sumCursors.p, 0, 2 * sizeof(unsigned long long), c->stream));
   FMT_HIP(c, hipEventRecord(c->evS0, c->stream));  // (own events: fmt_get_stats keeps reporting the replay)
   FMT_HIP(c, fmt_kernels::launchSummaryRuns(c->mtHdr.p, c->sumViews.p, nd, c->sumRuns.p, c->sumText.p, c->sumCursors.p,
@@ -2157,15 +2197,9 @@ int fmt_mt_summarize_legacy(fmt_ctx* c, const char* const* keys, uint32_t nKeys,
   for (uint32_t d = 0; d < nd; d++) {
     propOff[d + 1] = propOff[d] + hdr[d].n_props;
     if (hdr[d].n_props)
-      sp.push_back({reinterpret_cast<const uint32_t*>(propsDev[d]), propOff[d] * kPW, hdr[d].n_props * kPW, 0u});
+      sp.push_back({reinterpret_cast<const uint32_t*>(F->views[d].props), propOff[d] * kPW, hdr[d].n_props * kPW, 0u});
   }
-  if (!sp.empty()) {
-    FMT_HIP(c, c->spans.reserve(sp.size()));
-    FMT_HIP(c, c->packed.reserve(propOff[nd] * kPW));
-    FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
-                              c->stream));
-    FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
-  }
+  if (const int rc = gatherPacked(c, sp, propOff[nd] * kPW, nullptr, 0)) return rc;
   // (pinned destinations the ctx keeps: four DMAs back to back on the stream, one wait)
   FMT_HIP(c, c->sumHostDocs.reserve(nd));
   FMT_HIP(c, c->sumHostRuns.reserve(cur[0]));
@@ -2262,30 +2296,26 @@ int fmt_mt_summary_blobs(fmt_ctx* c, uint32_t doc, const char** header, size_t* 
 int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, const char* const* values, uint32_t nValues,
                         const char* const* clientNames, const uint64_t* docClientOffs, uint32_t chunk, uint32_t threads,
                         fmt_summary_timing* timing) {
-  if (c == nullptr || !c->mtLoaded || !c->mtRan || (nKeys && keys == nullptr) || (nValues && values == nullptr) ||
-      docClientOffs == nullptr || (docClientOffs[c->mtDocs] && clientNames == nullptr))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_summarize_v1: bad arguments, or no fmt_mt_run since the load");
+  const bool argsOk = c && c->mtLoaded && c->mtRan && !(nKeys && keys == nullptr) && !(nValues && values == nullptr) &&
+                      docClientOffs != nullptr && !(docClientOffs[c->mtDocs] && clientNames == nullptr);
+  if (const int rc = mtReadEntry(c, argsOk, nullptr, "fmt_mt_summarize_v1: bad arguments, or no fmt_mt_run since the load"))
+    return rc;
   if (c->mtPlan.local)
     return setErr(c, FMT_E_UNSUPPORTED, "fmt_mt_summarize_v1: the batch holds local-client records (pending stamps have no SnapshotV1 form)");
   using clk = std::chrono::steady_clock;
-  FMT_HIP(c, hipSetDevice(c->device));
   const uint32_t nd = c->mtDocs;
-  std::vector<fmt_mt_doc_result> hdr(nd);
-  FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-  FMT_HIP(c, hipStreamSynchronize(c->stream));
-  std::vector<fmt_kernels::SumView> views;
-  docViews(c, views);
+  const fmt_ctx::ReadFrame* F = readFrame(c);
+  if (F == nullptr) return FMT_E_DEVICE;
+  const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
   uint64_t capSegs = 0, capText = 0;
   for (uint32_t d = 0; d < nd; d++) {
     capSegs += hdr[d].n_leaves;
     capText += hdr[d].n_chars;
   }
-  FMT_HIP(c, c->sumViews.reserve(nd));
   FMT_HIP(c, c->v1Segs.reserve(capSegs));
   FMT_HIP(c, c->sumText.reserve(capText));
   FMT_HIP(c, c->sumCursors.reserve(2));
   FMT_HIP(c, c->sumDocs.reserve(nd));
-  FMT_HIP(c, hipMemcpyAsync(c->sumViews.p, views.data(), nd * sizeof(fmt_kernels::SumView), hipMemcpyHostToDevice, c->stream));
   FMT_HIP(c, hipMemsetAsync(c->sumCursors.p, 0, 2 * sizeof(unsigned long long), c->stream));
   FMT_HIP(c, hipEventRecord(c->evS0, c->stream));
   FMT_HIP(c, fmt_kernels::launchSummaryV1(c->mtHdr.p, c->sumViews.p, c->mtOps.p, c->mtOffs.p, nd, c->v1Segs.p, c->sumText.p,
@@ -2310,19 +2340,13 @@ int fmt_mt_summarize_v1(fmt_ctx* c, const char* const* keys, uint32_t nKeys, con
   std::vector<fmt_kernels::GatherSpan> sp;
   for (uint32_t d = 0; d < nd; d++) {
     if (propOff[d + 1] > propOff[d])
-      sp.push_back({reinterpret_cast<const uint32_t*>(views[d].props), propOff[d] * kPW,
+      sp.push_back({reinterpret_cast<const uint32_t*>(F->views[d].props), propOff[d] * kPW,
                     static_cast<uint32_t>(propOff[d + 1] - propOff[d]) * kPW, 0u});
     if (rmOff[d + 1] > rmOff[d])
       sp.push_back({reinterpret_cast<const uint32_t*>(c->mtRmOrder.p + c->mtPlan.rmOffs[d]), propOff[nd] * kPW + rmOff[d] * kRW,
                     static_cast<uint32_t>(rmOff[d + 1] - rmOff[d]) * kRW, 0u});
   }
-  if (!sp.empty()) {
-    FMT_HIP(c, c->spans.reserve(sp.size()));
-    FMT_HIP(c, c->packed.reserve(propOff[nd] * kPW + rmOff[nd] * kRW));
-    FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
-                              c->stream));
-    FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
-  }
+  if (const int rc = gatherPacked(c, sp, propOff[nd] * kPW + rmOff[nd] * kRW, nullptr, 0)) return rc;
   FMT_HIP(c, c->sumHostDocs.reserve(nd));
   FMT_HIP(c, c->v1HostSegs.reserve(cur[0]));
   FMT_HIP(c, c->sumHostText.reserve(cur[1]));
@@ -2429,9 +2453,9 @@ int fmt_mt_summary_v1_body(fmt_ctx* c, uint32_t doc, uint32_t k, const char** bo
 }
 
 int fmt_mt_fetch_catchup(fmt_ctx* c, uint32_t doc, fmt_mt_catchup_range* out, uint32_t cap) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_catchup: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_catchup");
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), "fmt_mt_fetch_catchup",
+                                 "fmt_mt_fetch_catchup: bad arguments"))
+    return rc;
   if (!c->mtPlan.hasCatchup()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
@@ -2441,18 +2465,17 @@ int fmt_mt_fetch_catchup(fmt_ctx* c, uint32_t doc, fmt_mt_catchup_range* out, ui
 }
 
 int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range* out, uint64_t cap) {
-  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_catchup_all: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_catchup_all");
-  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = mtReadEntry(c, offsets != nullptr, "fmt_mt_fetch_catchup_all", "fmt_mt_fetch_catchup_all: bad arguments"))
+    return rc;
   const uint32_t nd = c->mtDocs;
   offsets[0] = 0;
   if (!c->mtPlan.hasCatchup()) {
     for (uint32_t d = 0; d < nd; d++) offsets[d + 1] = 0;
     return FMT_OK;
   }
-  std::vector<fmt_mt_doc_result> hdr(nd);
-  FMT_HIP(c, hipMemcpy(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost));
+  const fmt_ctx::ReadFrame* F = readFrame(c);
+  if (F == nullptr) return FMT_E_DEVICE;
+  const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
   for (uint32_t d = 0; d < nd; d++) {
     const uint64_t slab = c->mtPlan.cuOffs[d + 1] - c->mtPlan.cuOffs[d];
     offsets[d + 1] = offsets[d] + std::min<uint64_t>(hdr[d].n_catchup, slab);
@@ -2468,57 +2491,33 @@ int fmt_mt_fetch_catchup_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_catchup_range
     if (offsets[d + 1] > offsets[d])
       sp.push_back({reinterpret_cast<const uint32_t*>(c->mtCatchup.p + c->mtPlan.cuOffs[d]), offsets[d] * kW,
                     static_cast<uint32_t>(offsets[d + 1] - offsets[d]) * kW, 0u});
-  if (offsets[nd] == 0) return FMT_OK;
-  FMT_HIP(c, c->spans.reserve(sp.size()));
-  FMT_HIP(c, c->packed.reserve(offsets[nd] * kW));
-  FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
-                            c->stream));
-  FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
-  FMT_HIP(c, stagedCopy(c, out, c->packed.p, offsets[nd] * sizeof(fmt_mt_catchup_range), false));
-  return FMT_OK;
+  return gatherPacked(c, sp, offsets[nd] * kW, out, offsets[nd] * sizeof(fmt_mt_catchup_range));
 }
 
 uint32_t fmt_mt_text_tile_leaves(void) { return fmt_plan::kTextTileLeaves; }
 
 int fmt_mt_fetch_text_all(fmt_ctx* c, uint16_t placeholder, uint64_t* offsets, uint16_t* out, uint64_t cap) {
-  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_text_all: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_text_all");
-  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = mtReadEntry(c, offsets != nullptr, "fmt_mt_fetch_text_all", "fmt_mt_fetch_text_all: bad arguments"))
+    return rc;
   const uint32_t nd = c->mtDocs;
-  // every document's result buffers. sumViews is shared with the summaries and the digest, so it is
-  // uploaded again ahead of each of the two launches (textViews lives in the ctx: the copy is asynchronous)
-  auto uploadViews = [&]() -> hipError_t {
-    docViews(c, c->textViews);
-    const hipError_t e = c->sumViews.reserve(nd);
-    return e != hipSuccess ? e
-                           : hipMemcpyAsync(c->sumViews.p, c->textViews.data(), nd * sizeof(fmt_kernels::SumView),
-                                            hipMemcpyHostToDevice, c->stream);
-  };
+  const fmt_ctx::ReadFrame* F = nullptr;
+  if (const int rc = frameTiles(c, "fmt_mt_fetch_text_all: more than 2^32 - 1 work items", &F)) return rc;
+  const size_t ni = F->tiles.items.size();
   if (!c->textSized || c->textPlaceholder != placeholder) {
-    // pass 1: the work items from the headers, the units each contributes, the scan on the host
+    // pass 1: the units each work item contributes under this placeholder, the scan on the host. (The tiles
+    // are the frame's and know no placeholder; only these units do.)
     c->textSized = false;
-    std::vector<fmt_mt_doc_result> hdr(nd);
-    FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-    FMT_HIP(c, hipStreamSynchronize(c->stream));
-    fmt_plan::planTextTiles(hdr.data(), nd, fmt_plan::kTextTileLeaves, c->textPlan);
-    const size_t ni = c->textPlan.items.size();
-    if (ni > 0xFFFFFFFFull) return setErr(c, FMT_E_CAPACITY, "fmt_mt_fetch_text_all: more than 2^32 - 1 work items");
-    FMT_HIP(c, c->textItems.reserve(ni));
     FMT_HIP(c, c->textUnits.reserve(ni));
     FMT_HIP(c, c->textBases.reserve(ni));
     FMT_HIP(c, c->textHostUnits.reserve(ni));
     FMT_HIP(c, c->textHostBases.reserve(ni));
     c->textOffs.assign(nd + 1ull, 0);
     if (ni) {
-      FMT_HIP(c, uploadViews());
-      FMT_HIP(c, hipMemcpyAsync(c->textItems.p, c->textPlan.items.data(), ni * sizeof(fmt_plan::TextItem),
-                                hipMemcpyHostToDevice, c->stream));
-      FMT_HIP(c, fmt_kernels::launchTextTileUnits(c->mtHdr.p, c->sumViews.p, c->textItems.p, static_cast<uint32_t>(ni),
+      FMT_HIP(c, fmt_kernels::launchTextTileUnits(c->mtHdr.p, c->sumViews.p, c->tileItems.p, static_cast<uint32_t>(ni),
                                                   placeholder, c->textUnits.p, c->numCUs, c->stream));
       FMT_HIP(c, hipMemcpyAsync(c->textHostUnits.p, c->textUnits.p, ni * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
       FMT_HIP(c, hipStreamSynchronize(c->stream));
-      fmt_plan::textOffsets(c->textPlan, c->textHostUnits.p, c->textOffs.data(), c->textHostBases.p);
+      fmt_plan::textOffsets(F->tiles, c->textHostUnits.p, c->textOffs.data(), c->textHostBases.p);
       FMT_HIP(c, hipMemcpyAsync(c->textBases.p, c->textHostBases.p, ni * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
       FMT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing of this call is in flight past here)
     }
@@ -2533,43 +2532,26 @@ int fmt_mt_fetch_text_all(fmt_ctx* c, uint16_t placeholder, uint64_t* offsets, u
   // pass 2: every item's units to its base in the packed text, then one staged copy of exactly those
   // (stagedCopy waits for the stream first and returns when the units are in `out`)
   FMT_HIP(c, c->textPacked.reserve(total));
-  FMT_HIP(c, uploadViews());
-  FMT_HIP(c, fmt_kernels::launchTextGather(c->mtHdr.p, c->sumViews.p, c->textItems.p,
-                                           static_cast<uint32_t>(c->textPlan.items.size()), placeholder, c->textBases.p,
-                                           c->textPacked.p, c->numCUs, c->stream));
+  FMT_HIP(c, fmt_kernels::launchTextGather(c->mtHdr.p, c->sumViews.p, c->tileItems.p, static_cast<uint32_t>(ni), placeholder,
+                                           c->textBases.p, c->textPacked.p, c->numCUs, c->stream));
   FMT_HIP(c, stagedCopy(c, out, c->textPacked.p, total * sizeof(uint16_t), false));
   return FMT_OK;
 }
 
 int fmt_mt_fetch_prop_runs_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_prop_run* out, uint64_t cap) {
-  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_prop_runs_all: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_prop_runs_all");
-  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = mtReadEntry(c, offsets != nullptr, "fmt_mt_fetch_prop_runs_all", "fmt_mt_fetch_prop_runs_all: bad arguments"))
+    return rc;
   const uint32_t nd = c->mtDocs;
-  // sumViews is shared with the summaries, the digest and the text read: uploaded again ahead of the
-  // launches of each call (runsViews lives in the ctx: the copy is asynchronous). The views carry the
-  // huge documents' own classes (docViews: SumView::cls).
-  auto uploadViews = [&]() -> hipError_t {
-    docViews(c, c->runsViews);
-    const hipError_t e = c->sumViews.reserve(nd);
-    return e != hipSuccess ? e
-                           : hipMemcpyAsync(c->sumViews.p, c->runsViews.data(), nd * sizeof(fmt_kernels::SumView),
-                                            hipMemcpyHostToDevice, c->stream);
-  };
+  const fmt_ctx::ReadFrame* F = nullptr;
+  if (const int rc = frameTiles(c, "fmt_mt_fetch_prop_runs_all: more than 2^32 - 1 work items", &F)) return rc;
+  const size_t ni = F->tiles.items.size();
   if (!c->runsSized) {
-    // the work items and the class spans from the headers, the classes, pass 1, the stitch on the host
-    std::vector<fmt_mt_doc_result> hdr(nd);
-    FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-    FMT_HIP(c, hipStreamSynchronize(c->stream));
-    fmt_plan::planTextTiles(hdr.data(), nd, fmt_plan::kTextTileLeaves, c->runsPlan);
-    const size_t ni = c->runsPlan.items.size();
-    if (ni > 0xFFFFFFFFull) return setErr(c, FMT_E_CAPACITY, "fmt_mt_fetch_prop_runs_all: more than 2^32 - 1 work items");
-    docViews(c, c->runsViews);
+    // the class spans from the headers (the views carry the huge documents' own classes, SumView::cls), the
+    // classes, pass 1, the stitch on the host
+    const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
     c->runsClsOffs.assign(nd + 1ull, 0);
     for (uint32_t d = 0; d < nd; d++)
-      c->runsClsOffs[d + 1] = c->runsClsOffs[d] + (hdr[d].status == FMT_OK && c->runsViews[d].cls == nullptr ? hdr[d].n_props : 0u);
-    FMT_HIP(c, c->runsItems.reserve(ni));
+      c->runsClsOffs[d + 1] = c->runsClsOffs[d] + (hdr[d].status == FMT_OK && F->views[d].cls == nullptr ? hdr[d].n_props : 0u);
     FMT_HIP(c, c->runsClsOff.reserve(nd + 1ull));
     FMT_HIP(c, c->runsCls.reserve(c->runsClsOffs[nd]));
     FMT_HIP(c, c->runsTiles.reserve(ni));
@@ -2578,18 +2560,15 @@ int fmt_mt_fetch_prop_runs_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_prop_run* o
     FMT_HIP(c, c->runsHostBases.reserve(ni));
     c->runsOffs.assign(nd + 1ull, 0);
     if (ni) {
-      FMT_HIP(c, uploadViews());
-      FMT_HIP(c, hipMemcpyAsync(c->runsItems.p, c->runsPlan.items.data(), ni * sizeof(fmt_plan::TextItem),
-                                hipMemcpyHostToDevice, c->stream));
       FMT_HIP(c, hipMemcpyAsync(c->runsClsOff.p, c->runsClsOffs.data(), (nd + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice,
                                 c->stream));
       if (c->runsClsOffs[nd])
         FMT_HIP(c, fmt_kernels::launchRunClasses(c->mtHdr.p, c->sumViews.p, nd, c->runsClsOff.p, c->runsCls.p, c->numCUs, c->stream));
-      FMT_HIP(c, fmt_kernels::launchRunTileReport(c->mtHdr.p, c->sumViews.p, c->runsItems.p, static_cast<uint32_t>(ni),
+      FMT_HIP(c, fmt_kernels::launchRunTileReport(c->mtHdr.p, c->sumViews.p, c->tileItems.p, static_cast<uint32_t>(ni),
                                                   c->runsClsOff.p, c->runsCls.p, c->runsTiles.p, c->numCUs, c->stream));
       FMT_HIP(c, hipMemcpyAsync(c->runsHostTiles.p, c->runsTiles.p, ni * sizeof(fmt_plan::RunTile), hipMemcpyDeviceToHost, c->stream));
       FMT_HIP(c, hipStreamSynchronize(c->stream));
-      fmt_plan::stitchRuns(c->runsPlan, c->runsHostTiles.p, c->runsOffs.data(), c->runsHostBases.p);
+      fmt_plan::stitchRuns(F->tiles, c->runsHostTiles.p, c->runsOffs.data(), c->runsHostBases.p);
       FMT_HIP(c, hipMemcpyAsync(c->runsBases.p, c->runsHostBases.p, ni * sizeof(fmt_plan::RunTileBase), hipMemcpyHostToDevice, c->stream));
       FMT_HIP(c, hipStreamSynchronize(c->stream));  // (nothing of this call is in flight past here)
     }
@@ -2602,79 +2581,56 @@ int fmt_mt_fetch_prop_runs_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_prop_run* o
   if (total == 0) return FMT_OK;
   // pass 2: every item's runs to its base in the packed runs, then one staged copy of exactly those
   FMT_HIP(c, c->runsPacked.reserve(total));
-  FMT_HIP(c, uploadViews());
-  FMT_HIP(c, fmt_kernels::launchRunEmit(c->mtHdr.p, c->sumViews.p, c->runsItems.p, static_cast<uint32_t>(c->runsPlan.items.size()),
-                                        c->runsClsOff.p, c->runsCls.p, c->runsBases.p, total, c->runsPacked.p, c->numCUs,
-                                        c->stream));
+  FMT_HIP(c, fmt_kernels::launchRunEmit(c->mtHdr.p, c->sumViews.p, c->tileItems.p, static_cast<uint32_t>(ni), c->runsClsOff.p,
+                                        c->runsCls.p, c->runsBases.p, total, c->runsPacked.p, c->numCUs, c->stream));
   FMT_HIP(c, stagedCopy(c, out, c->runsPacked.p, total * sizeof(fmt_mt_prop_run), false));
   return FMT_OK;
 }
 
 int fmt_mt_fetch_props_all(fmt_ctx* c, uint64_t* offsets, fmt_mt_propset* out, uint64_t cap) {
-  if (c == nullptr || !c->mtLoaded || offsets == nullptr)
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_props_all: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_props_all");
-  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = mtReadEntry(c, offsets != nullptr, "fmt_mt_fetch_props_all", "fmt_mt_fetch_props_all: bad arguments"))
+    return rc;
   const uint32_t nd = c->mtDocs;
-  std::vector<fmt_mt_doc_result> hdr(nd);
-  FMT_HIP(c, hipMemcpy(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost));
+  const fmt_ctx::ReadFrame* F = readFrame(c);
+  if (F == nullptr) return FMT_E_DEVICE;
+  const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
   offsets[0] = 0;
   for (uint32_t d = 0; d < nd; d++) offsets[d + 1] = offsets[d] + (hdr[d].status == FMT_OK ? hdr[d].n_props : 0u);
   if (out == nullptr) return FMT_OK;
   if (cap < offsets[nd]) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_props_all: cap below the number of prop-set records");
-  if (offsets[nd] == 0) return FMT_OK;
   // each document's records packed on the device (gatherSpansKernel), then one staged copy of exactly those
   constexpr uint32_t kPW = sizeof(fmt_mt_propset) / 4;
-  std::vector<fmt_kernels::SumView> views;
-  docViews(c, views);
   std::vector<fmt_kernels::GatherSpan> sp;
   sp.reserve(nd);
   for (uint32_t d = 0; d < nd; d++)
     if (offsets[d + 1] > offsets[d])
-      sp.push_back({reinterpret_cast<const uint32_t*>(views[d].props), offsets[d] * kPW,
+      sp.push_back({reinterpret_cast<const uint32_t*>(F->views[d].props), offsets[d] * kPW,
                     static_cast<uint32_t>(offsets[d + 1] - offsets[d]) * kPW, 0u});
-  FMT_HIP(c, c->spans.reserve(sp.size()));
-  FMT_HIP(c, c->packed.reserve(offsets[nd] * kPW));
-  FMT_HIP(c, hipMemcpyAsync(c->spans.p, sp.data(), sp.size() * sizeof(fmt_kernels::GatherSpan), hipMemcpyHostToDevice,
-                            c->stream));
-  FMT_HIP(c, fmt_kernels::launchGatherSpans(c->spans.p, static_cast<uint32_t>(sp.size()), c->packed.p, c->numCUs, c->stream));
-  FMT_HIP(c, stagedCopy(c, out, c->packed.p, offsets[nd] * sizeof(fmt_mt_propset), false));
-  return FMT_OK;
+  return gatherPacked(c, sp, offsets[nd] * kPW, out, offsets[nd] * sizeof(fmt_mt_propset));
 }
 
 int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_pos_query* q, uint64_t nQueries,
                            fmt_mt_pos_hit* out) {
-  if (c == nullptr || !c->mtLoaded || qOffsets == nullptr || (nQueries && (q == nullptr || out == nullptr)))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_query_positions: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_query_positions");
+  if (const int rc = mtReadEntry(c, qOffsets != nullptr && !(nQueries && (q == nullptr || out == nullptr)), "fmt_mt_query_positions",
+                                 "fmt_mt_query_positions: bad arguments"))
+    return rc;
   const uint32_t nd = c->mtDocs;
   if (!fmt_plan::posOffsetsValid(qOffsets, nd, nQueries))
     return setErr(c, FMT_E_USAGE, "fmt_mt_query_positions: q_offsets must ascend from 0 to n_queries");
   if (nQueries == 0) return FMT_OK;
-  FMT_HIP(c, hipSetDevice(c->device));
-  // the statuses the headers decide, the views and their (view, tile) items
-  std::vector<fmt_mt_doc_result> hdr(nd);
-  FMT_HIP(c, hipMemcpyAsync(hdr.data(), c->mtHdr.p, nd * sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  // the statuses the headers decide, the views and their (view, tile) items over the frame's tiles
+  const fmt_ctx::ReadFrame* F = nullptr;
+  if (const int frc = frameTiles(c, "fmt_mt_query_positions: more than 2^32 - 1 views or work items", &F)) return frc;
+  const std::vector<fmt_mt_doc_result>& hdr = F->hdr;
   fmt_plan::PosPlan& P = c->posPlan;
-  const int rc = fmt_plan::planPosViews(hdr.data(), nd, c->mtPlan.obliterates, fmt_plan::kTextTileLeaves, qOffsets, q, nQueries, out, P);
+  const int rc = fmt_plan::planPosViews(hdr.data(), nd, c->mtPlan.obliterates, F->tiles, qOffsets, q, nQueries, out, P);
   if (rc != FMT_OK) return setErr(c, rc, "fmt_mt_query_positions: more than 2^32 - 1 views or work items");
-  // sumViews is shared with the summaries, the digest, the text and the runs reads: uploaded again ahead of
-  // each launch (posViews lives in the ctx: the copy is asynchronous)
-  auto uploadViews = [&]() -> hipError_t {
-    docViews(c, c->posViews);
-    const hipError_t e = c->sumViews.reserve(nd);
-    return e != hipSuccess ? e
-                           : hipMemcpyAsync(c->sumViews.p, c->posViews.data(), nd * sizeof(fmt_kernels::SumView),
-                                            hipMemcpyHostToDevice, c->stream);
-  };
   // pass 1: every item's units in its view and in the local view; the prefixes and the tile lookup on the host
   const size_t ni = P.items.size();
   FMT_HIP(c, c->posHostUnits.reserve(ni));
   if (ni) {
     FMT_HIP(c, c->posItems.reserve(ni));
     FMT_HIP(c, c->posUnits.reserve(ni));
-    FMT_HIP(c, uploadViews());
     FMT_HIP(c, hipMemcpyAsync(c->posItems.p, P.items.data(), ni * sizeof(fmt_plan::PosItem), hipMemcpyHostToDevice, c->stream));
     FMT_HIP(c, fmt_kernels::launchPosTileUnits(c->mtHdr.p, c->sumViews.p, c->posItems.p, static_cast<uint32_t>(ni), c->posUnits.p,
                                                c->numCUs, c->stream));
@@ -2682,7 +2638,7 @@ int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_po
                               c->stream));
     FMT_HIP(c, hipStreamSynchronize(c->stream));
   }
-  fmt_plan::resolvePosQueries(P, hdr.data(), c->posHostUnits.p, q, nQueries, out);
+  fmt_plan::resolvePosQueries(P, F->tiles, hdr.data(), c->posHostUnits.p, q, nQueries, out);
   const size_t nDev = P.dev.size();
   if (nDev == 0) return FMT_OK;
   // pass 2: the records as the host left them go up, every device query's lane writes its own, and one
@@ -2691,7 +2647,6 @@ int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_po
   FMT_HIP(c, c->posHits.reserve(nQueries));
   FMT_HIP(c, stagedCopy(c, c->posHits.p, out, nQueries * sizeof(fmt_mt_pos_hit), true));
   FMT_HIP(c, stagedCopy(c, c->posQueries.p, P.dev.data(), nDev * sizeof(fmt_plan::PosDevQuery), true));
-  FMT_HIP(c, uploadViews());
   FMT_HIP(c, fmt_kernels::launchPosResolve(c->mtHdr.p, c->sumViews.p, c->posQueries.p, nDev, nQueries, c->posHits.p, c->numCUs,
                                            c->stream));
   FMT_HIP(c, stagedCopy(c, out, c->posHits.p, nQueries * sizeof(fmt_mt_pos_hit), false));
@@ -2699,9 +2654,9 @@ int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_po
 }
 
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_remove_order: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_remove_order");
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), "fmt_mt_fetch_remove_order",
+                                 "fmt_mt_fetch_remove_order: bad arguments"))
+    return rc;
   if (!c->mtPlan.hasRmOrder()) return FMT_OK;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
@@ -2712,15 +2667,13 @@ int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out
 
 // word 0 of every leaf (ids 64..127), or words 1 and 2 (ids 128..191, 192..253) with `upper`
 static int fetchRmClientsHi(fmt_ctx* c, uint32_t doc, uint64_t* out, uint32_t cap, bool upper, const char* what) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
-    return setErr(c, FMT_E_USAGE, std::string(what) + ": bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, what);
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), what, std::string(what) + ": bad arguments"))
+    return rc;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t per = upper ? fmt_huge::kHiOutWords - 1 : 1;
   const uint32_t m = h.n_leaves < cap / per ? h.n_leaves : cap / per;
-  const int32_t hs = doc < c->mtHugeSlot.size() ? c->mtHugeSlot[doc] : -1;
-  const uint64_t* src = hs >= 0 ? c->huge[static_cast<size_t>(hs)].out.leavesHi : nullptr;
+  const uint64_t* src = docView(c, doc).rmHi;
   if (src != nullptr && m) {
     std::vector<uint64_t> all(static_cast<size_t>(m) * fmt_huge::kHiOutWords);
     FMT_HIP(c, hipMemcpy(all.data(), src, all.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -2741,31 +2694,30 @@ int fmt_mt_fetch_rm_clients_hi2(fmt_ctx* c, uint32_t doc, uint64_t* out, uint32_
 }
 
 int fmt_mt_fetch_legacy_props(fmt_ctx* c, uint32_t doc, uint16_t* out, uint32_t cap) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_legacy_props: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_legacy_props");
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), "fmt_mt_fetch_legacy_props",
+                                 "fmt_mt_fetch_legacy_props: bad arguments"))
+    return rc;
   fmt_mt_doc_result h;
   FMT_HIP(c, hipMemcpy(&h, c->mtHdr.p + doc, sizeof h, hipMemcpyDeviceToHost));
   const uint32_t m = h.n_leaves < cap ? h.n_leaves : cap;
   if (m == 0) return FMT_OK;
-  std::vector<fmt_kernels::SumView> views;
-  docViews(c, views);
-  if (views[doc].legacyProps != nullptr) {
-    FMT_HIP(c, hipMemcpy(out, views[doc].legacyProps, m * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  const fmt_kernels::SumView V = docView(c, doc);
+  if (V.legacyProps != nullptr) {
+    FMT_HIP(c, hipMemcpy(out, V.legacyProps, m * sizeof(uint16_t), hipMemcpyDeviceToHost));
     if (out[0] == fmt_mt::kLegacyUnavailable)  // (the engine marks every leaf)
       return setErr(c, FMT_E_CAPACITY, "fmt_mt_fetch_legacy_props: the document's getAtSeq view did not fit its prop-set table");
     return FMT_OK;
   }
   std::vector<fmt_mt_leaf> lv(m);  // (no annotate-adjust in the batch: getAtSeq is the current properties)
-  FMT_HIP(c, hipMemcpy(lv.data(), views[doc].leaves, m * sizeof(fmt_mt_leaf), hipMemcpyDeviceToHost));
+  FMT_HIP(c, hipMemcpy(lv.data(), V.leaves, m * sizeof(fmt_mt_leaf), hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < m; i++) out[i] = lv[i].props;
   return FMT_OK;
 }
 
 int fmt_mt_fetch_numbers(fmt_ctx* c, uint32_t doc, double* out, uint32_t cap, uint32_t* nOut) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (out == nullptr && cap > 0))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_numbers: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_numbers");
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), "fmt_mt_fetch_numbers",
+                                 "fmt_mt_fetch_numbers: bad arguments"))
+    return rc;
   uint32_t n = 0;
   if (c->mtPlan.anyAdjust) FMT_HIP(c, hipMemcpy(&n, c->mtNumCount.p + doc, sizeof n, hipMemcpyDeviceToHost));
   if (nOut) *nOut = n;
@@ -2776,9 +2728,9 @@ int fmt_mt_fetch_numbers(fmt_ctx* c, uint32_t doc, double* out, uint32_t cap, ui
 
 int fmt_mt_fetch_regen(fmt_ctx* c, uint32_t doc, fmt_mt_op* ops, uint32_t capOps, uint16_t* text, uint32_t capText,
                        uint32_t* nOps, uint32_t* nText) {
-  if (c == nullptr || !c->mtLoaded || doc >= c->mtDocs || (ops == nullptr && capOps > 0) || (text == nullptr && capText > 0))
-    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_regen: bad arguments");
-  if (!c->mtRan) return mtNeedsRun(c, "fmt_mt_fetch_regen");
+  if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(ops == nullptr && capOps > 0) && !(text == nullptr && capText > 0),
+                                 "fmt_mt_fetch_regen", "fmt_mt_fetch_regen: bad arguments"))
+    return rc;
   uint32_t cnt[2] = {0, 0};
   if (c->mtPlan.local) FMT_HIP(c, hipMemcpy(cnt, c->mtLocRegenCount.p + 2ull * doc, sizeof cnt, hipMemcpyDeviceToHost));
   if (nOps) *nOps = cnt[0];
@@ -2918,8 +2870,10 @@ int fmt_internal_pos_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_
   if ((nDocs && hdrs == nullptr) || qOffsets == nullptr || (nQueries && (q == nullptr || hits == nullptr)) || out == nullptr ||
       nWords == nullptr)
     return FMT_E_USAGE;
+  fmt_plan::TextPlan T;
+  fmt_plan::planTextTiles(hdrs, nDocs, tileLeaves, T);
   fmt_plan::PosPlan P;
-  const int rc = fmt_plan::planPosViews(hdrs, nDocs, obliterates != 0, tileLeaves, qOffsets, q, nQueries, hits, P);
+  const int rc = fmt_plan::planPosViews(hdrs, nDocs, obliterates != 0, T, qOffsets, q, nQueries, hits, P);
   if (rc != FMT_OK) return rc;
   auto sx = [](int32_t x) { return static_cast<uint64_t>(static_cast<int64_t>(x)); };
   w.assign(1, P.views.size());
@@ -2931,7 +2885,7 @@ int fmt_internal_pos_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_
     static_assert(sizeof(fmt_plan::PosTileUnits) == 2 * sizeof(uint64_t), "PosTileUnits is two words");
     std::vector<fmt_plan::PosTileUnits> u(P.items.size() + 1);
     std::memcpy(u.data(), tileUnits, P.items.size() * sizeof(fmt_plan::PosTileUnits));
-    fmt_plan::resolvePosQueries(P, hdrs, u.data(), q, nQueries, hits);
+    fmt_plan::resolvePosQueries(P, T, hdrs, u.data(), q, nQueries, hits);
     w.push_back(P.dev.size());
     for (const fmt_plan::PosDevQuery& d : P.dev)
       w.insert(w.end(), {uint64_t{d.doc}, uint64_t{d.firstLeaf}, uint64_t{d.nLeaves}, uint64_t{d.pos}, sx(d.refSeq), sx(d.client),

@@ -1,5 +1,6 @@
 // sum_wave.h — the wave-level helpers the bulk summary kernels share (summary.hip, summary_v1.hip):
-// one wave per document, match classes of prop sets in LDS.
+// one wave per document, match classes of prop sets in LDS; and the ones of the readers that deal one
+// wave per work item (text.hip, runs.hip, pos.hip): the item clamp, the lane scan, the item loop, the grid.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,6 +40,36 @@ __device__ __forceinline__ bool sumSameSet(const fmt_mt_propset* T, uint32_t p, 
     if (!found) return false;
   }
   return true;
+}
+
+// ---- one wave per work item, kSumWaves waves per workgroup, items dealt grid-stride
+
+// The leaves of the tile [firstLeaf, firstLeaf + nLeaves) that the document of header h has: 0 when it failed.
+__device__ __forceinline__ uint32_t waveItemLeaves(const fmt_mt_doc_result& h, uint32_t firstLeaf, uint32_t nLeaves) {
+  const int32_t status = h.status;
+  const uint32_t n = h.n_leaves;
+  if (status != FMT_OK || firstLeaf >= n) return 0;
+  return nLeaves < n - firstLeaf ? nLeaves : n - firstLeaf;
+}
+
+// Inclusive prefix of x over the wave's 64 lanes.
+__device__ __forceinline__ uint32_t waveScan(uint32_t x, int lane) {
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = static_cast<uint32_t>(__shfl_up(static_cast<int>(x), o));
+    if (lane >= o) x += t;
+  }
+  return x;
+}
+
+// A wave's items: for (uint64_t k = waveItemFirst(); k < n; k += waveItemStride()).
+__device__ __forceinline__ uint64_t waveItemFirst() { return static_cast<uint64_t>(blockIdx.x) * kSumWaves + (threadIdx.x >> 6); }
+__device__ __forceinline__ uint64_t waveItemStride() { return static_cast<uint64_t>(gridDim.x) * kSumWaves; }
+
+// Workgroups for n items (host): one wave each up to 8 workgroups per CU, the rest by stride; at least 1.
+inline uint32_t waveGrid(uint64_t n, int numCUs) {
+  const uint64_t wanted = (n + kSumWaves - 1) / kSumWaves;
+  const uint64_t cap = static_cast<uint64_t>(numCUs) * 8u;
+  return static_cast<uint32_t>(wanted < cap ? (wanted > 0 ? wanted : 1) : cap);
 }
 
 }  // namespace fmt_kernels

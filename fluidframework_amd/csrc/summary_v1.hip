@@ -171,11 +171,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void summaryV1Kernel(const fmt_mt_d
         }
       }
       // text: emitted leaves' units to text[textBase + tpos + prefix]
-      uint32_t ex = len;  // exclusive prefix of len over lanes
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = static_cast<uint32_t>(__shfl_up(static_cast<int>(ex), o));
-        if (lane >= o) ex += t;
-      }
+      uint32_t ex = waveScan(len, lane);  // inclusive, then exclusive prefix of len over the lanes
       const uint32_t chunkUnits = sumUni(static_cast<uint32_t>(__shfl(static_cast<int>(ex), 63)));
       ex -= len;
       for (uint32_t u0 = 0; u0 < chunkUnits; u0 += 64) {

@@ -26,14 +26,6 @@ namespace fmt_kernels {
 
 namespace {
 
-// The leaves of item `it` that exist: 0 for a document that failed.
-__device__ __forceinline__ uint32_t textItemLeaves(const fmt_mt_doc_result* hdrs, const fmt_plan::TextItem& it) {
-  const int32_t status = hdrs[it.doc].status;
-  const uint32_t n = hdrs[it.doc].n_leaves;
-  if (status != FMT_OK || it.firstLeaf >= n) return 0;
-  return it.nLeaves < n - it.firstLeaf ? it.nLeaves : n - it.firstLeaf;
-}
-
 __device__ __forceinline__ uint32_t textUnitsOf(const fmt_mt_leaf& L, uint32_t placeholder) {
   if (L.rm_seq != FMT_NOT_REMOVED) return 0;
   if ((L.pad & FMT_MT_LEAF_MARKER) != 0) return placeholder != 0 ? 1u : 0u;
@@ -47,12 +39,10 @@ __global__ __launch_bounds__(64 * kSumWaves) void textTileUnitsKernel(const fmt_
                                                                 const fmt_plan::TextItem* __restrict__ items,
                                                                 uint32_t nItems, uint32_t placeholder,
                                                                 unsigned long long* __restrict__ tileUnits) {
-  const uint32_t wave = threadIdx.x >> 6;
   const uint32_t lane = threadIdx.x & 63;
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nItems;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nItems; k += waveItemStride()) {
     const fmt_plan::TextItem it = items[k];
-    const uint32_t n = textItemLeaves(hdrs, it);
+    const uint32_t n = waveItemLeaves(hdrs[it.doc], it.firstLeaf, it.nLeaves);
     const fmt_mt_leaf* leaves = views[it.doc].leaves + it.firstLeaf;
     unsigned long long acc = 0;
     for (uint32_t b = 0; b < n; b += 64) {
@@ -70,12 +60,10 @@ __global__ __launch_bounds__(64 * kSumWaves) void textGatherKernel(const fmt_mt_
                                                              uint32_t nItems, uint32_t placeholder,
                                                              const unsigned long long* __restrict__ tileBase,
                                                              uint16_t* __restrict__ packed) {
-  const uint32_t wave = threadIdx.x >> 6;
   const int lane = static_cast<int>(threadIdx.x & 63);
-  for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * kSumWaves + wave; k < nItems;
-       k += static_cast<uint64_t>(gridDim.x) * kSumWaves) {
+  for (uint64_t k = waveItemFirst(); k < nItems; k += waveItemStride()) {
     const fmt_plan::TextItem it = items[k];
-    const uint32_t n = textItemLeaves(hdrs, it);
+    const uint32_t n = waveItemLeaves(hdrs[it.doc], it.firstLeaf, it.nLeaves);
     const SumView V = views[it.doc];
     const fmt_mt_leaf* leaves = V.leaves + it.firstLeaf;
     uint16_t* dst = packed + tileBase[k];
@@ -89,11 +77,7 @@ __global__ __launch_bounds__(64 * kSumWaves) void textGatherKernel(const fmt_mt_
         off = L.char_off;
         marker = (L.pad & FMT_MT_LEAF_MARKER) != 0 ? 1u : 0u;
       }
-      uint32_t ex = len;  // inclusive, then exclusive prefix of len over the lanes
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = static_cast<uint32_t>(__shfl_up(static_cast<int>(ex), o));
-        if (lane >= o) ex += t;
-      }
+      uint32_t ex = waveScan(len, lane);  // inclusive, then exclusive prefix of len over the lanes
       const uint32_t chunkUnits = sumUni(static_cast<uint32_t>(__shfl(static_cast<int>(ex), 63)));
       ex -= len;
       for (uint32_t u0 = 0; u0 < chunkUnits; u0 += 64) {
@@ -114,16 +98,10 @@ __global__ __launch_bounds__(64 * kSumWaves) void textGatherKernel(const fmt_mt_
   }
 }
 
-static uint32_t textGrid(uint32_t nItems, int numCUs) {
-  const uint32_t wanted = (nItems + kSumWaves - 1) / kSumWaves;
-  const uint32_t cap = static_cast<uint32_t>(numCUs) * 8u;
-  return wanted < cap ? (wanted > 0 ? wanted : 1) : cap;
-}
-
 hipError_t launchTextTileUnits(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
                                uint32_t nItems, uint16_t placeholder, unsigned long long* tileUnits, int numCUs,
                                hipStream_t stream) {
-  hipLaunchKernelGGL(textTileUnitsKernel, dim3(textGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
+  hipLaunchKernelGGL(textTileUnitsKernel, dim3(waveGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
                      items, nItems, static_cast<uint32_t>(placeholder), tileUnits);
   return hipGetLastError();
 }
@@ -131,7 +109,7 @@ hipError_t launchTextTileUnits(const fmt_mt_doc_result* hdrs, const SumView* vie
 hipError_t launchTextGather(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::TextItem* items,
                             uint32_t nItems, uint16_t placeholder, const unsigned long long* tileBase, uint16_t* packed,
                             int numCUs, hipStream_t stream) {
-  hipLaunchKernelGGL(textGatherKernel, dim3(textGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
+  hipLaunchKernelGGL(textGatherKernel, dim3(waveGrid(nItems, numCUs)), dim3(64 * kSumWaves), 0, stream, hdrs, views,
                      items, nItems, static_cast<uint32_t>(placeholder), tileBase, packed);
   return hipGetLastError();
 }

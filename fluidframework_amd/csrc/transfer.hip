@@ -8,10 +8,11 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "sum_wave.h"
 
 namespace fmt_kernels {
 
-constexpr int kGatherWaves = 4;
+constexpr int kGatherWaves = kSumWaves;  // (waveGrid sizes the grid)
 
 __global__ __launch_bounds__(64 * kGatherWaves) void gatherSpansKernel(const GatherSpan* __restrict__ spans, uint32_t n,
                                                                        uint32_t* __restrict__ dst) {
@@ -26,10 +27,7 @@ __global__ __launch_bounds__(64 * kGatherWaves) void gatherSpansKernel(const Gat
 
 hipError_t launchGatherSpans(const GatherSpan* spans, uint32_t n, uint32_t* dst, int numCUs, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  const uint32_t wanted = (n + kGatherWaves - 1) / kGatherWaves;
-  const uint32_t cap = static_cast<uint32_t>(numCUs) * 8u;
-  const uint32_t grid = wanted < cap ? wanted : cap;
-  hipLaunchKernelGGL(gatherSpansKernel, dim3(grid), dim3(64 * kGatherWaves), 0, stream, spans, n, dst);
+  hipLaunchKernelGGL(gatherSpansKernel, dim3(waveGrid(n, numCUs)), dim3(64 * kGatherWaves), 0, stream, spans, n, dst);
   return hipGetLastError();
 }
 

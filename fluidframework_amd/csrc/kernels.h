@@ -8,6 +8,7 @@
 #include "../../include/fmt_runs.h"
 #include "map_plan.h"
 #include "mt_bind.h"
+#include "mt_route.h"
 #include "pos_plan.h"
 #include "runs_plan.h"
 #include "text_plan.h"
@@ -169,37 +170,36 @@ struct MtCaps {
 };
 MtCaps mergeTreeCaps(bool large);
 
-// Micro + compact + small tiers: replays documents docList[0..count) (or all docs when docList ==
-// nullptr); documents that overflow the small tier are listed in esc (esc[0] = count, then ids) when
-// esc != nullptr. A batch without remove order with esc2 != nullptr starts in the compact tier and
-// lists its overflow in esc2 (count + 1 entries) for the small tier; without obliterates either and
-// with esc4 != nullptr it starts in the micro tier (mergetree_micro.hip), whose overflow list the
-// compact tier replays, listing its own in esc4 (count + 1 entries). esc3 (count + 1 entries): where a
-// list is reordered by remaining ops. esc[0], esc2[0] and esc4[0] must be zero before the call. sched:
-// 4 zeroed device counters (compact, small, large, micro) from which the tiers deal documents to waves
-// dynamically (nullptr: static grid-stride shares). adjust: the batch holds annotate-adjust entries
-// (the Adj engine variants, small tier first, no checkpoints). desc: mergeTreeDescendWords(count) zeroed
-// words (the lists and dealing counters of the rounds in which documents that shrank step down a tier:
-// plain batches with checkpoints and esc3), or nullptr: one round, a document only ever moves up.
-hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
-                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust,
-                           uint32_t* desc = nullptr);
-size_t mergeTreeDescendWords(uint32_t count);
+// The device lists and counters a route's steps name (mt_route.h MtList / MtDeal), built in one place
+// (runtime.cpp). Every list holds count + 1 words, [0] = n, then ids. toLarge[0], microUp[0], compactUp[0], the
+// four sched counters (compact, small, large, micro) and the whole of desc (mergeTreeDescendWords words) must
+// be zero before launchMergeTree. docs / count: the caller's list (MtListKind::kCaller), or nullptr.
+struct MtLists {
+  uint32_t* toLarge = nullptr;
+  uint32_t* microUp = nullptr;
+  uint32_t* compactUp = nullptr;
+  uint32_t* ordered = nullptr;
+  uint32_t* sched = nullptr;
+  uint32_t* desc = nullptr;  // nullptr: not allocated for this batch (the route then has one round)
+  size_t descWords = 0;
+  const uint32_t* docs = nullptr;
+  uint32_t count = 0;
+};
+struct MtLaunchEnv {
+  int numCUs;
+  hipStream_t stream;
+};
 
-// Large tier over docList[0..count): out.leaves/chars/props are slabs indexed by list position.
-hipError_t launchMergeTreeLarge(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                uint32_t count, int numCUs, hipStream_t stream, bool obliterate, bool removeOrder,
-                                uint32_t* next, bool adjust, bool local = false);
+// The register tiers: walks route.steps (mt_route.h planRoute), one mergeTreeKernel launch plus one
+// collectOverflowKernel launch a step, and one orderByRemainingKernel launch before a step whose list is
+// reordered. Every list length stays on the device. The documents left for the large pass are in lists.toLarge.
+hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const fmt_plan::MtRoute& route,
+                           const MtLists& lists, const MtLaunchEnv& env);
 
-// f4 local-client batches (round 6): the small tier's local variant over docList[0..count) (or every
-// document; FMT_LOCAL_PATH selects a compact-tier pass first, documents it cannot hold listed in esc2),
-// the ones it cannot hold listed in esc (esc[0] = count, then ids) for launchMergeTreeLarge(..., local =
-// true). esc[0] and esc2[0] zeroed by the caller; sched: zeroed dealing counters (compact, small).
-// adjust: annotate-adjust batches, the small tier's Adj local variant.
-hipError_t launchMergeTreeLocal(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                uint32_t count, uint32_t* esc, uint32_t* esc2, int numCUs, hipStream_t stream,
-                                uint32_t* sched, bool adjust = false);
+// The large pass (route.large) over the `count` documents of lists.toLarge, dealt from the large counter:
+// out.leaves/chars/props are slabs indexed by list position.
+hipError_t launchMergeTreeLarge(const MtDeviceBatch& batch, const MtDeviceOut& out, const fmt_plan::MtRoute& route,
+                                const MtLists& lists, uint32_t count, const MtLaunchEnv& env);
 
 // Diagnostic: per-phase cycle totals of a FMT_PROFILE=1 build (all zero otherwise).
 int mergeTreeProfile(uint64_t* out, int n, bool reset);

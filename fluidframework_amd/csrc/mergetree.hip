@@ -1,16 +1,14 @@
 // mergetree.hip — merge-tree replay, small tier (8 register rows: 512 leaves, 2 waves/SIMD), the
 // overflow-list kernel and the tier cascade (kernel template: mergetree_kernel.h).
 //
-// A plain batch replays every document in the micro tier first (mergetree_micro.hip: 2 rows); the
-// documents it overflows go on in the compact tier (mergetree_compact.hip: 4 rows) from a device-side
-// list, and those that one overflows in this tier from a second list; those this tier overflows go to
-// the large tier (mergetree_large.hip) after the host reads the list length. With checkpoints the
-// compact and small tiers run kDescendRounds times: in every round but the last a small-tier document
-// that shrank to half of the compact tier stops (fmt_mt::kCkptDescend) and goes on a "down" list, which
-// the compact tier replays in the next round, so it pays for the rows it has, not for the rows it once
-// had. Every list length stays on the device; a round whose lists are empty costs launches that exit
-// at once. Batches with obliterates start in the compact tier; batches with remove-order recording or
-// adjusts start in this tier; neither steps down.
+// The cascade itself is planned on the host (mt_route.h planRoute): a plain batch replays every document
+// in the micro tier first (mergetree_micro.hip: 2 rows); the documents it overflows go on in the compact
+// tier (mergetree_compact.hip: 4 rows) from a device-side list, and those that one overflows in this
+// tier from a second list; those this tier overflows go to the large tier (mergetree_large.hip) after
+// the host reads the list length. With checkpoints the compact and small tiers run kDescendRounds
+// times, so that a document that shrank pays for the rows it has, not for the rows it once had.
+// Batches with obliterates start in the compact tier; batches with remove-order recording or adjusts
+// start in this tier; neither steps down. launchMergeTree below walks the route's steps.
 #define FMT_MT_COLLECT_DEFINE 1
 #include "mergetree_kernel.h"
 
@@ -40,22 +38,10 @@ MtCaps mergeTreeCaps(bool large) {
 
 size_t mergeTreeCheckpointBytes() { return sizeof(uint32_t) * fmt_mt::Doc<false, fmt_mt::CompactTier>::kCkptWords; }
 
-hipError_t launchMergeTreeCompact(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                  uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next,
-                                  bool obliterate, const uint32_t* countDev);
-hipError_t launchMergeTreeMicro(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next);
-
-// Rounds of the plain cascade (see the header comment). DESIGN.md §4.1 has the hop counts behind it.
-#ifndef FMT_DESCEND_ROUNDS
-#define FMT_DESCEND_ROUNDS 2
-#endif
-constexpr int kDescendRounds = FMT_DESCEND_ROUNDS;  // (1: a document only ever moves up)
-constexpr size_t kDescendHead = 64;  // dealing counters of the rounds after the first, 2 a round
-
-size_t mergeTreeDescendWords(uint32_t count) {
-  return kDescendHead + static_cast<size_t>(2 * (kDescendRounds - 1)) * (static_cast<size_t>(count) + 1);
-}
+// one variant switch per translation unit
+hipError_t launchMicroTier(fmt_plan::MtVariant v, const TierLaunch& a);
+hipError_t launchCompactTier(fmt_plan::MtVariant v, const TierLaunch& a);
+hipError_t launchLocalTier(fmt_plan::MtTier tier, fmt_plan::MtVariant v, const TierLaunch& a);
 
 // A tier's overflow list in[0] = n, in[1..n] reordered into out by remaining ops,
 // longest first (64 buckets between 0 and the largest remainder): with documents dealt to waves
@@ -103,79 +89,68 @@ __global__ __launch_bounds__(1024) void orderByRemainingKernel(const uint32_t* _
   }
 }
 
-// Variants: obliterates (Ob) and/or the remove-order recording of SnapshotV1 batches (Rm).
-hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                           uint32_t count, uint32_t* esc, uint32_t* esc2, uint32_t* esc3, uint32_t* esc4, int numCUs,
-                           hipStream_t stream, bool obliterate, bool removeOrder, uint32_t* sched, bool adjust,
-                           uint32_t* desc) {
+// Variants: obliterates (Ob) and/or the remove-order recording of SnapshotV1 batches (Rm); annotate-adjust
+// batches run the Adj variants.
+static hipError_t launchSmallTier(fmt_plan::MtVariant v, const TierLaunch& a) {
   using S = fmt_mt::SmallTier;
-  uint32_t* n1 = sched ? sched + 1 : nullptr;
-  if (adjust) {  // annotate-adjust batches: the Adj variants, small tier over every document (no checkpoints)
-    // (1 wave/SIMD: 512 registers a wave; at 2 the property-manager code spilled 3710 VGPRs to scratch,
+  using fmt_plan::mtKey;
+  switch (v.key()) {
+    // (Adj, 1 wave/SIMD: 512 registers a wave; at 2 the property-manager code spilled 3710 VGPRs to scratch,
     // at 1 the overflow lives in AGPRs)
-    if (removeOrder)
-      return launchTier<true, S, true, kMtWaves, 1, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-    return launchTier<true, S, false, kMtWaves, 1, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
+    case mtKey(true, true, true): return launchTier<true, S, true, kMtWaves, 1, true>(a);
+    case mtKey(true, false, true): return launchTier<true, S, false, kMtWaves, 1, true>(a);
+    case mtKey(true, true): return launchTier<true, S, true, kMtWaves, 2>(a);
+    case mtKey(true, false): return launchTier<true, S, false, kMtWaves, 2>(a);
+    case mtKey(false, true): return launchTier<false, S, true, kMtWaves, 2>(a);
+    case mtKey(false, false): return launchTier<false, S, false, kMtWaves, 2>(a);
   }
-  if (obliterate && removeOrder)
-    return launchTier<true, S, true, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  if (obliterate && (esc == nullptr || esc2 == nullptr))
-    return launchTier<true, S, false, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  if (removeOrder)
-    return launchTier<false, S, true, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  if (esc == nullptr || esc2 == nullptr)
-    return launchTier<false, S, false, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launchMergeTree(const MtDeviceBatch& batch, const MtDeviceOut& out, const fmt_plan::MtRoute& route,
+                           const MtLists& lists, const MtLaunchEnv& env) {
+  using fmt_plan::MtListKind;
+  using fmt_plan::MtTier;
   constexpr uint32_t kCkptWords = static_cast<uint32_t>(fmt_mt::Doc<false, fmt_mt::CompactTier>::kCkptWords);
-  const bool order = esc3 != nullptr && out.ckpt != nullptr;  // longest remaining streams first
-  hipError_t e;
-  if (!obliterate && esc4 != nullptr) {
-    // Round 0: micro tier over everything → overflow list esc2 → compact tier over that list → overflow
-    // list esc4 → this tier over that list → overflow list esc. Every list is reordered into esc3 first
-    // (order). Without checkpoints (out.ckpt == nullptr) each tier restarts its documents from their
-    // first op, and nothing steps down.
-    // Round r > 0 (desc: two lists a round): compact tier over this tier's down list of round r - 1 →
-    // this tier over the compact tier's overflow → esc, appended. The last round lets nothing step
-    // down, so every document finishes (or is in esc).
-    const int rounds = order && desc != nullptr ? kDescendRounds : 1;
-    const size_t stride = static_cast<size_t>(count) + 1;
-    const auto roundList = [&](int r, int k) { return desc + kDescendHead + (static_cast<size_t>(2 * (r - 1) + k)) * stride; };
-    const auto ordered = [&](uint32_t* list) {
-      if (!order) return list;
-      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, list, esc3, out.headers,
-                         batch.docOpOffsets, out.ckpt, kCkptWords);
-      return esc3;
-    };
-    e = launchMergeTreeMicro(batch, out, docList, count, esc2, numCUs, stream, sched ? sched + 3 : nullptr);
-    if (e != hipSuccess) return e;
-    for (int r = 0; r < rounds; r++) {
-      MtDeviceOut o = out;
-      o.descend = r + 1 < rounds;
-      uint32_t* toCompact = r == 0 ? esc2 : roundList(r, 0);
-      uint32_t* toSmall = r == 0 ? esc4 : roundList(r, 1);
-      uint32_t* down = o.descend ? roundList(r + 1, 0) : nullptr;  // → the next round's compact tier
-      uint32_t* deal = sched && r > 0 ? desc + 2 * (r - 1) : nullptr;
-      const uint32_t* list = ordered(toCompact);
-      e = launchMergeTreeCompact(batch, o, list + 1, count, toSmall, numCUs, stream, r == 0 ? sched : deal, false, list);
-      if (e != hipSuccess) return e;
-      list = ordered(toSmall);
-      e = launchTier<false, S, false, kMtWaves, 2>(batch, o, list + 1, count, esc, numCUs, stream, list,
-                                                   r == 0 ? n1 : (deal ? deal + 1 : nullptr), down);
-      if (e != hipSuccess) return e;
+  if (route.nSteps == 0) return hipSuccess;
+  const bool caller = route.steps[0].in.kind == MtListKind::kCaller;
+  if ((caller && lists.docs == nullptr) || (route.rounds > 1 && lists.desc == nullptr)) return hipErrorInvalidValue;
+  // every launch's bound on its list, and the stride of the step-down slab's lists
+  const uint32_t count = caller ? lists.count : batch.nDocs;
+  const auto list = [&](fmt_plan::MtList l) -> uint32_t* {
+    switch (l.kind) {
+      case MtListKind::kMicroUp: return lists.microUp;
+      case MtListKind::kCompactUp: return lists.compactUp;
+      case MtListKind::kToLarge: return lists.toLarge;
+      case MtListKind::kOrdered: return lists.ordered;
+      case MtListKind::kRound:
+        return lists.desc + fmt_plan::kDescendHead + static_cast<size_t>(2 * (l.r - 1) + l.k) * (static_cast<size_t>(count) + 1);
+      default: return nullptr;
     }
-    return hipSuccess;
+  };
+  for (int i = 0; i < route.nSteps; i++) {
+    const fmt_plan::MtStep& s = route.steps[i];
+    MtDeviceOut o = out;
+    o.descend = s.descend;
+    const uint32_t* in = s.in.onDevice() ? list(s.in) : nullptr;
+    if (in != nullptr && s.orderInto.kind != MtListKind::kNone) {  // longest remaining streams first
+      uint32_t* ordered = list(s.orderInto);
+      hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, env.stream, in, ordered, out.headers,
+                         batch.docOpOffsets, out.ckpt, kCkptWords);
+      in = ordered;
+    }
+    uint32_t* next = s.deal.kind == fmt_plan::MtDealKind::kRound ? lists.desc + 2 * (s.deal.r - 1) + s.deal.k
+                                                                 : lists.sched + static_cast<int>(s.deal.kind);
+    const TierLaunch a{batch, o, in ? in + 1 : caller ? lists.docs : nullptr, count, list(s.up), env.numCUs, env.stream, in,
+                       next, list(s.down)};
+    const hipError_t e = s.variant.loc               ? launchLocalTier(s.tier, s.variant, a)
+                         : s.tier == MtTier::kMicro   ? launchMicroTier(s.variant, a)
+                         : s.tier == MtTier::kCompact ? launchCompactTier(s.variant, a)
+                         : s.tier == MtTier::kSmall   ? launchSmallTier(s.variant, a)
+                                                      : hipErrorInvalidValue;
+    if (e != hipSuccess) return e;
   }
-  // obliterate batches: compact tier over everything → overflow list esc2 → this tier over that list →
-  // overflow list esc
-  e = launchMergeTreeCompact(batch, out, docList, count, esc2, numCUs, stream, sched, obliterate, nullptr);
-  if (e != hipSuccess) return e;
-  if (order) {
-    hipLaunchKernelGGL(orderByRemainingKernel, dim3(1), dim3(1024), 0, stream, esc2, esc3, out.headers,
-                       batch.docOpOffsets, out.ckpt, kCkptWords);
-    esc2 = esc3;
-  }
-  if (obliterate)
-    return launchTier<true, S, false, kMtWaves, 2>(batch, out, esc2 + 1, count, esc, numCUs, stream, esc2, n1);
-  return launchTier<false, S, false, kMtWaves, 2>(batch, out, esc2 + 1, count, esc, numCUs, stream, esc2, n1);
+  return hipSuccess;
 }
 
 }  // namespace fmt_kernels

@@ -12,16 +12,15 @@ constexpr int kMtWavesCompact = 4;  // 4 documents per workgroup
 
 int mergeTreeProfileCompact(uint64_t* out, int n, bool reset) { return addTuProfile(out, n, reset); }
 
-// countDev: the documents are the micro tier's overflow list (its length on the device); those it left
+// a.countDev: the documents are the micro tier's overflow list (its length on the device); those it left
 // at a checkpoint resume from it.
-hipError_t launchMergeTreeCompact(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                  uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next,
-                                  bool obliterate, const uint32_t* countDev) {
-  if (obliterate)  // Doc<true>: the same 4 rows plus the live-obliterate table (163 VGPRs)
-    return launchTier<true, fmt_mt::CompactTier, false, kMtWavesCompact, 3>(batch, out, docList, count, esc, numCUs,
-                                                                           stream, countDev, next);
-  return launchTier<false, fmt_mt::CompactTier, false, kMtWavesCompact, 4>(batch, out, docList, count, esc, numCUs,
-                                                                          stream, countDev, next);
+hipError_t launchCompactTier(fmt_plan::MtVariant v, const TierLaunch& a) {
+  switch (v.key()) {
+    // Doc<true>: the same 4 rows plus the live-obliterate table (163 VGPRs)
+    case fmt_plan::mtKey(true, false): return launchTier<true, fmt_mt::CompactTier, false, kMtWavesCompact, 3>(a);
+    case fmt_plan::mtKey(false, false): return launchTier<false, fmt_mt::CompactTier, false, kMtWavesCompact, 4>(a);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace fmt_kernels

@@ -97,11 +97,33 @@ __global__ __launch_bounds__(256) void collectOverflowKernel(fmt_mt_doc_result* 
 }
 #endif
 
-// countDev: the list length lives on the device (an overflow list); `count` then bounds it (grid size).
+// One launch of a tier. docList / count: the documents (nullptr: 0 .. count); countDev: the list length
+// lives on the device (an overflow list), `count` then bounds it (grid size). esc / down: the lists
+// collectOverflowKernel appends to (esc nullptr: none is collected). next: the dealing counter, or nullptr.
+struct TierLaunch {
+  const MtDeviceBatch& batch;
+  const MtDeviceOut& out;
+  const uint32_t* docList;
+  uint32_t count;
+  uint32_t* esc;
+  int numCUs;
+  hipStream_t stream;
+  const uint32_t* countDev;
+  uint32_t* next;
+  uint32_t* down;
+};
+
+template <class C>
+constexpr fmt_plan::MtTier tierOf() {
+  return C::kHbmChars                            ? fmt_plan::MtTier::kLarge
+         : C::kRows == fmt_mt::MicroTier::kRows   ? fmt_plan::MtTier::kMicro
+         : C::kRows == fmt_mt::CompactTier::kRows ? fmt_plan::MtTier::kCompact
+                                                  : fmt_plan::MtTier::kSmall;
+}
+
 template <bool Ob, class C, bool Rm, int Waves, int WavesPerEU, bool Adj = false, bool Loc = false>
-static hipError_t launchTier(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                             uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream,
-                             const uint32_t* countDev = nullptr, uint32_t* next = nullptr, uint32_t* down = nullptr) {
+static hipError_t launchTier(const TierLaunch& a) {
+  static_assert(fmt_plan::hasMtKernel(tierOf<C>(), fmt_plan::MtVariant{Ob, Rm, Adj, Loc}), "not in mt_route.h kMtKernels");
   const size_t lds = scratchBytes<C, Ob>() * Waves;
   // One resident wave of workgroups: every workgroup strides over the same number of documents,
   // so none waits behind the residency limit (VGPRs cap the small tier at 2 waves/SIMD).
@@ -109,15 +131,15 @@ static hipError_t launchTier(const MtDeviceBatch& batch, const MtDeviceOut& out,
   const hipError_t e =
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, mergeTreeKernel<Ob, C, Rm, Waves, WavesPerEU, Adj, Loc>, 64 * Waves, lds);
   if (e != hipSuccess) return e;
-  const uint32_t wanted = (count + Waves - 1) / Waves;
-  const uint32_t cap = static_cast<uint32_t>(numCUs * (blocksPerCU > 0 ? blocksPerCU : 1));
+  const uint32_t wanted = (a.count + Waves - 1) / Waves;
+  const uint32_t cap = static_cast<uint32_t>(a.numCUs * (blocksPerCU > 0 ? blocksPerCU : 1));
   const uint32_t grid = wanted < cap ? (wanted > 0 ? wanted : 1) : cap;
-  hipLaunchKernelGGL((mergeTreeKernel<Ob, C, Rm, Waves, WavesPerEU, Adj, Loc>), dim3(grid), dim3(64 * Waves), lds, stream, batch, out,
-                     docList, count, countDev, next);
-  if (esc != nullptr) {  // over the documents this launch replayed
-    const uint32_t g = (count + 255) / 256;
-    hipLaunchKernelGGL(collectOverflowKernel, dim3(g < 1024 ? (g > 0 ? g : 1) : 1024), dim3(256), 0, stream, out.headers,
-                       docList, count, countDev, esc, down);
+  hipLaunchKernelGGL((mergeTreeKernel<Ob, C, Rm, Waves, WavesPerEU, Adj, Loc>), dim3(grid), dim3(64 * Waves), lds, a.stream, a.batch,
+                     a.out, a.docList, a.count, a.countDev, a.next);
+  if (a.esc != nullptr) {  // over the documents this launch replayed
+    const uint32_t g = (a.count + 255) / 256;
+    hipLaunchKernelGGL(collectOverflowKernel, dim3(g < 1024 ? (g > 0 ? g : 1) : 1024), dim3(256), 0, a.stream, a.out.headers,
+                       a.docList, a.count, a.countDev, a.esc, a.down);
   }
   return hipGetLastError();
 }

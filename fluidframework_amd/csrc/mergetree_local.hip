@@ -14,33 +14,25 @@
 namespace fmt_kernels {
 
 constexpr int kMtWavesLocal = 4;  // 4 documents per workgroup
-// 0: compact → large; 1: small → large (kept: the reference farms' writer views overflow the compact
-// tier in 17 of 28 streams; A/B at 20k documents 383 ms against 410 for 2 and 1379 for 0,
-// profiles/r6/local2/ab_local.json); 2: compact → small → large (tools/build_variants.py loc*)
-#ifndef FMT_LOCAL_PATH
-#define FMT_LOCAL_PATH 1
-#endif
+// Which of them a batch takes: mt_route.h FMT_LOCAL_PATH. 0: compact → large; 1: small → large (kept: the
+// reference farms' writer views overflow the compact tier in 17 of 28 streams; A/B at 20k documents 383 ms
+// against 410 for 2 and 1379 for 0, profiles/r6/local2/ab_local.json); 2: compact → small → large
 
-hipError_t launchMergeTreeLocal(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                uint32_t count, uint32_t* esc, uint32_t* esc2, int numCUs, hipStream_t stream,
-                                uint32_t* sched, bool adjust) {
+hipError_t launchLocalTier(fmt_plan::MtTier tier, fmt_plan::MtVariant v, const TierLaunch& a) {
   using K = fmt_mt::CompactTier;
   using S = fmt_mt::SmallTier;
-  uint32_t* n0 = sched, * n1 = sched ? sched + 1 : nullptr;
-  // annotate-adjust batches (round 6): the PropertiesManager's remote and local change lists with
-  // adjust folding (Doc<..., Adj, Loc>), small tier first whatever FMT_LOCAL_PATH says
-  if (adjust)
-    return launchTier<false, S, false, kMtWavesLocal, 2, true, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  if constexpr (FMT_LOCAL_PATH == 0)
-    return launchTier<false, K, false, kMtWavesLocal, 3, false, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n0);
-  if constexpr (FMT_LOCAL_PATH == 1)
-    return launchTier<false, S, false, kMtWavesLocal, 2, false, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);
-  // compact over everything → overflow list esc2 → the small tier over that list → overflow list esc
-  if constexpr (FMT_LOCAL_PATH != 2) return hipErrorInvalidValue;
-  hipError_t e = launchTier<false, K, false, kMtWavesLocal, 3, false, true>(batch, out, docList, count, esc2, numCUs, stream,
-                                                                            nullptr, n0);
-  if (e != hipSuccess) return e;
-  return launchTier<false, S, false, kMtWavesLocal, 2, false, true>(batch, out, esc2 + 1, count, esc, numCUs, stream, esc2, n1);
+  using fmt_plan::MtTier;
+  switch (v.key() | static_cast<uint32_t>(tier) << 4) {
+    // annotate-adjust batches (round 6): the PropertiesManager's remote and local change lists with
+    // adjust folding (Doc<..., Adj, Loc>), small tier first whatever FMT_LOCAL_PATH says
+    case fmt_plan::mtKey(false, false, true, true) | static_cast<uint32_t>(MtTier::kSmall) << 4:
+      return launchTier<false, S, false, kMtWavesLocal, 2, true, true>(a);
+    case fmt_plan::mtKey(false, false, false, true) | static_cast<uint32_t>(MtTier::kSmall) << 4:
+      return launchTier<false, S, false, kMtWavesLocal, 2, false, true>(a);
+    case fmt_plan::mtKey(false, false, false, true) | static_cast<uint32_t>(MtTier::kCompact) << 4:
+      return launchTier<false, K, false, kMtWavesLocal, 3, false, true>(a);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace fmt_kernels

@@ -16,10 +16,11 @@ constexpr int kMtWavesMicro = 4;  // 4 documents per workgroup
 
 int mergeTreeProfileMicro(uint64_t* out, int n, bool reset) { return addTuProfile(out, n, reset); }
 
-hipError_t launchMergeTreeMicro(const MtDeviceBatch& batch, const MtDeviceOut& out, const uint32_t* docList,
-                                uint32_t count, uint32_t* esc, int numCUs, hipStream_t stream, uint32_t* next) {
-  return launchTier<false, fmt_mt::MicroTier, false, kMtWavesMicro, 4>(batch, out, docList, count, esc, numCUs, stream,
-                                                                      nullptr, next);
+hipError_t launchMicroTier(fmt_plan::MtVariant v, const TierLaunch& a) {
+  switch (v.key()) {
+    case fmt_plan::mtKey(false, false): return launchTier<false, fmt_mt::MicroTier, false, kMtWavesMicro, 4>(a);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace fmt_kernels

@@ -25,6 +25,7 @@
 #include "jsnum.h"
 #include "mt_engine.h"  // fmt_mt::AdjustTables
 #include "mt_plan.h"
+#include "mt_route_words.h"
 #include "map_sum_plan.h"
 #include "kernels.h"
 
@@ -173,16 +174,14 @@ struct fmt_ctx {
   DevBuf<fmt_mt_leaf> mtLeaves;
   DevBuf<uint16_t> mtChars;
   DevBuf<fmt_mt_propset> mtProps;
-  DevBuf<uint32_t> mtEsc;                    // small-tier overflow list: [0] = count, then doc ids
-  DevBuf<uint32_t> mtEsc2;                   // compact-tier overflow list (no remove order), same layout
-  DevBuf<uint32_t> mtEsc3;                   // the same list, longest remaining streams first
-  DevBuf<uint32_t> mtEsc4;                   // plain batches: the compact tier's list when the micro tier's is in mtEsc2
+  // the device lists and dealing counters a route's steps name (kernels.h MtLists), and what they point into:
+  // mtListBuf (the four per-tier counters, then four lists of n_docs + 1 words) and mtDesc (the step-down rounds)
+  fmt_kernels::MtLists mtLists;
+  DevBuf<uint32_t> mtListBuf, mtDesc;
   DevBuf<uint32_t> mtCkpt;                   // per-document compact → small tier checkpoints
-  DevBuf<uint32_t> mtDesc;                   // plain batches: lists and dealing counters of the step-down rounds
-  size_t mtDescWords = 0;                    // (0: not allocated for this batch, a document only moves up)
   DevBuf<uint32_t> mtHugeCk;                 // per large-tier slot: its large → huge checkpoint record (huge_ckpt.h)
   bool mtCkptOk = false;                     // allocated for this batch (else tiers replay overflow from op 0)
-  DevBuf<uint32_t> mtSched;                  // per-tier document counters (dynamic dealing to waves)
+  fmt_plan::MtRoute mtRoute;                 // how this batch goes through the tiers (planned at load)
   DevBuf<fmt_mt_leaf> mtBigLeaves;           // large-tier result slabs, one per escalated doc
   DevBuf<uint16_t> mtBigChars;
   DevBuf<fmt_mt_propset> mtBigProps;
@@ -592,11 +591,7 @@ void fmt_close(fmt_ctx* c) {
   c->mtLeaves.release();
   c->mtChars.release();
   c->mtProps.release();
-  c->mtEsc.release();
-  c->mtEsc2.release();
-  c->mtEsc3.release();
-  c->mtEsc4.release();
-  c->mtSched.release();
+  c->mtListBuf.release();
   c->mtCkpt.release();
   c->mtDesc.release();
   c->mtHugeCk.release();
@@ -1466,11 +1461,7 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   FMT_HIP(c, c->mtLeaves.reserve(static_cast<size_t>(n) * caps.leaves));
   FMT_HIP(c, c->mtChars.reserve(static_cast<size_t>(n) * caps.chars));
   FMT_HIP(c, c->mtProps.reserve(static_cast<size_t>(n) * caps.props));
-  FMT_HIP(c, c->mtEsc.reserve(n + 1ull));
-  FMT_HIP(c, c->mtEsc2.reserve(n + 1ull));
-  FMT_HIP(c, c->mtEsc3.reserve(n + 1ull));
-  FMT_HIP(c, c->mtEsc4.reserve(n + 1ull));
-  FMT_HIP(c, c->mtSched.reserve(4));
+  FMT_HIP(c, c->mtListBuf.reserve(4 + 4 * (n + 1ull)));
   c->mtBigSlot.assign(n, -1);
   // catch-up and remove-order slabs (sizes: mt_plan.h catchupSlab / rmOrderSlab)
   if (P.hasCatchup()) {
@@ -1603,12 +1594,15 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     if (!c->mtCkptOk) (void)hipGetLastError();
   }
   // plain batches with checkpoints: the lists of the rounds in which documents step down a tier
-  c->mtDescWords = 0;
-  if (c->mtCkptOk && !P.obliterates && !P.anyAdjust && !P.local) {
-    const size_t words = fmt_kernels::mergeTreeDescendWords(n);
-    if (c->mtDesc.reserve(words) == hipSuccess) c->mtDescWords = words;
-    else (void)hipGetLastError();
+  size_t descWords = 0;
+  if (fmt_plan::routeUsesDescSlab(P, c->mtCkptOk)) {
+    descWords = fmt_plan::mergeTreeDescendWords(n);
+    if (c->mtDesc.reserve(descWords) != hipSuccess) {
+      (void)hipGetLastError();
+      descWords = 0;
+    }
   }
+  c->mtRoute = fmt_plan::planRoute(P, c->mtCkptOk, descWords > 0);
   // Huge documents: a summary-loaded document with more segments or text than the large tier holds
   // is replayed by the huge-document engine (huge_engine.h: one wave, state in HBM). One the plan
   // refused (local-client records), or whose state does not fit in device memory, fails alone at load
@@ -1647,6 +1641,13 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
     FMT_HIP(c, c->mtSmallList.reserve(small.size()));
     FMT_HIP(c, cp(c->mtSmallList.p, small.data(), small.size() * sizeof(uint32_t)));
   }
+  {  // (mtListBuf: the counters, then toLarge, microUp, compactUp, ordered)
+    uint32_t* w = c->mtListBuf.p;
+    const size_t stride = n + 1ull;
+    c->mtLists = fmt_kernels::MtLists{w + 4, w + 4 + stride, w + 4 + 2 * stride, w + 4 + 3 * stride, w,
+                                      descWords > 0 ? c->mtDesc.p : nullptr, descWords,
+                                      c->mtUseList ? c->mtSmallList.p : nullptr, c->mtUseList ? c->mtNSmall : 0u};
+  }
   const int rc = uploadHuge(c, 0, c->hugeStates, c->hugeInputs, c->hugeOuts);
   if (rc != FMT_OK) return rc;
   FMT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1654,154 +1655,176 @@ int fmt_mt_load(fmt_ctx* c, const fmt_mt_batch* b) {
   return FMT_OK;
 }
 
-int fmt_mt_run(fmt_ctx* c) {
-  if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
-  c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
-  invalidateReads(c);
-  FMT_HIP(c, hipSetDevice(c->device));
-  // documents an earlier run of this load escalated into the huge tier start over: their state is
-  // released, and only the load-time huge documents (c->mtHugeLoaded) run with the small tiers
+// ------------------------------------------------------------------ fmt_mt_run, in parts
+static fmt_kernels::MtDeviceBatch mtBatchView(const fmt_ctx* c) {
+  return fmt_kernels::MtDeviceBatch{c->mtOps.p, c->mtOffs.p, c->mtDocs, c->mtText.p,
+                                    c->mtHasInit ? c->mtInit.p : nullptr, c->mtPropsOff.p, c->mtPropsKv.p, c->mtNProps,
+                                    c->mtPlan.hasCatchup() ? c->mtCuOffs.p : nullptr,
+                                    c->mtHasSnap ? c->mtSnap.p : nullptr, c->mtHasSnap ? c->mtSnapSegs.p : nullptr,
+                                    c->mtPlan.hasRmOrder() ? c->mtRmOffs.p : nullptr,
+                                    c->mtHasSnapInfo ? c->mtSnapInfo.p : nullptr, c->mtHasSnapInfo ? c->mtSnapStamps.p : nullptr,
+                                    c->mtHasSnapInfo ? c->mtNSnapSegs : 0u, c->mtNRelpos ? c->mtRelpos.p : nullptr,
+                                    c->mtNRelpos, c->mtMarkerKey, c->mtPlan.anyAdjust ? c->mtAdjTab.p : nullptr,
+                                    c->mtPlan.local ? c->mtLocTab.p : nullptr};
+}
+
+// What a launch writes to, from the route's booleans: the register tiers' slabs, or the large pass's.
+static fmt_kernels::MtDeviceOut mtOutView(const fmt_ctx* c, bool large, uint32_t* hugeCk = nullptr) {
+  const fmt_plan::MtRoute& R = c->mtRoute;
+  const bool ckpt = large ? R.largeCkpt : R.tiersCkpt, small = large && R.largeResumesSmall;
+  return fmt_kernels::MtDeviceOut{c->mtHdr.p, large ? c->mtBigLeaves.p : c->mtLeaves.p, large ? c->mtBigChars.p : c->mtChars.p,
+                                  large ? c->mtBigProps.p : c->mtProps.p, c->mtPlan.hasCatchup() ? c->mtCatchup.p : nullptr,
+                                  c->mtPlan.hasRmOrder() ? c->mtRmOrder.p : nullptr, ckpt ? c->mtCkpt.p : nullptr,
+                                  small ? c->mtLeaves.p : nullptr, small ? c->mtChars.p : nullptr,
+                                  !c->mtPlan.anyAdjust ? nullptr : large ? c->mtBigLegacy.p : c->mtLegacy.p, hugeCk};
+}
+
+// The list heads, the per-tier dealing counters and the step-down slab, zeroed for a run.
+static int zeroMtLists(fmt_ctx* c) {
+  const fmt_kernels::MtLists& L = c->mtLists;
+  for (uint32_t* head : {L.toLarge, L.microUp, L.compactUp}) FMT_HIP(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+  FMT_HIP(c, hipMemsetAsync(L.sched, 0, 4 * sizeof(uint32_t), c->stream));
+  if (L.descWords > 0) FMT_HIP(c, hipMemsetAsync(L.desc, 0, L.descWords * sizeof(uint32_t), c->stream));
+  return FMT_OK;
+}
+
+// Documents an earlier run escalated into the huge tier start over: only the load-time ones (mtHugeLoaded) stay.
+static int releaseGrownHuge(fmt_ctx* c) {
   FMT_HIP(c, hipStreamSynchronize(c->stream));
   for (size_t h = c->mtHugeLoaded; h < c->huge.size(); h++)
     for (void* q : c->huge[h].allocs) (void)hipFree(q);
   for (uint32_t d = 0; d < c->mtDocs; d++)
     if (c->mtHugeSlot[d] >= static_cast<int32_t>(c->mtHugeLoaded)) c->mtHugeSlot[d] = -1;
   c->huge.resize(c->mtHugeLoaded);
-  fmt_kernels::MtDeviceBatch db{c->mtOps.p, c->mtOffs.p, c->mtDocs, c->mtText.p,
-                                c->mtHasInit ? c->mtInit.p : nullptr, c->mtPropsOff.p, c->mtPropsKv.p, c->mtNProps,
-                                c->mtPlan.hasCatchup() ? c->mtCuOffs.p : nullptr,
-                                c->mtHasSnap ? c->mtSnap.p : nullptr, c->mtHasSnap ? c->mtSnapSegs.p : nullptr,
-                                c->mtPlan.hasRmOrder() ? c->mtRmOffs.p : nullptr,
-                                c->mtHasSnapInfo ? c->mtSnapInfo.p : nullptr, c->mtHasSnapInfo ? c->mtSnapStamps.p : nullptr,
-                                c->mtHasSnapInfo ? c->mtNSnapSegs : 0u,
-                                c->mtNRelpos ? c->mtRelpos.p : nullptr,
-                                c->mtNRelpos, c->mtMarkerKey,
-                                c->mtPlan.anyAdjust ? c->mtAdjTab.p : nullptr,
-                                c->mtPlan.local ? c->mtLocTab.p : nullptr};
-  fmt_kernels::MtDeviceOut dout{c->mtHdr.p, c->mtLeaves.p, c->mtChars.p, c->mtProps.p,
-                                c->mtPlan.hasCatchup() ? c->mtCatchup.p : nullptr, c->mtPlan.hasRmOrder() ? c->mtRmOrder.p : nullptr,
-                                !c->mtPlan.hasRmOrder() && !c->mtPlan.anyAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr, nullptr, nullptr,
-                                c->mtPlan.anyAdjust ? c->mtLegacy.p : nullptr};
-  FMT_HIP(c, hipMemsetAsync(c->mtEsc.p, 0, sizeof(uint32_t), c->stream));
-  FMT_HIP(c, hipMemsetAsync(c->mtEsc2.p, 0, sizeof(uint32_t), c->stream));
-  FMT_HIP(c, hipMemsetAsync(c->mtEsc4.p, 0, sizeof(uint32_t), c->stream));
-  FMT_HIP(c, hipMemsetAsync(c->mtSched.p, 0, 4 * sizeof(uint32_t), c->stream));
-  if (c->mtDescWords > 0) FMT_HIP(c, hipMemsetAsync(c->mtDesc.p, 0, c->mtDescWords * sizeof(uint32_t), c->stream));
+  return FMT_OK;
+}
+
+// The route's register tiers (mt_route.h) and the load-time huge documents, between ev0 and ev1.
+static int launchRegisterTiers(fmt_ctx* c, const fmt_kernels::MtDeviceBatch& db) {
+  if (const int rc = zeroMtLists(c)) return rc;
   FMT_HIP(c, hipEventRecord(c->ev0, c->stream));
-  const bool hasHuge = c->mtHugeLoaded > 0, list = c->mtUseList;
-  if (c->mtPlan.local) {
-    // f4 (round 6): the small tier's local variant over every document (its Adj variant for
-    // annotate-adjust batches); those listed in mtEsc replay from their first op in the large tier's
-    // local variant below (mergetree_local.hip)
-    if (!list || c->mtNSmall > 0)
-      FMT_HIP(c, fmt_kernels::launchMergeTreeLocal(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
-                                                   c->mtEsc.p, c->mtEsc2.p, c->numCUs, c->stream, c->mtSched.p,
-                                                   c->mtPlan.anyAdjust));
-  } else if (!list || c->mtNSmall > 0)
-    FMT_HIP(c, fmt_kernels::launchMergeTree(db, dout, list ? c->mtSmallList.p : nullptr, list ? c->mtNSmall : c->mtDocs,
-                                            c->mtEsc.p, c->mtEsc2.p, c->mtEsc3.p, c->mtEsc4.p, c->numCUs, c->stream,
-                                            c->mtPlan.obliterates,
-                                            c->mtPlan.hasRmOrder(), c->mtSched.p, c->mtPlan.anyAdjust,
-                                            c->mtDescWords > 0 ? c->mtDesc.p : nullptr));
-  if (hasHuge)
+  if (!c->mtUseList || c->mtNSmall > 0)
+    FMT_HIP(c, fmt_kernels::launchMergeTree(db, mtOutView(c, false), c->mtRoute, c->mtLists, {c->numCUs, c->stream}));
+  if (c->mtHugeLoaded > 0)
     FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates.p, c->hugeInputs.p, c->hugeOuts.p, c->mtHugeLoaded, c->mtPlan.anyAdjust, c->mtPlan.hasRmOrder(), c->stream));
   FMT_HIP(c, hipEventRecord(c->ev1, c->stream));  // device time excludes the host read-back below
   c->timed2 = false;
-  // Documents that overflowed the small tier replay again, from their inputs, in the large tier.
+  return FMT_OK;
+}
+
+// The nEsc > 0 documents the register tiers left replay in the large tier, between ev2 and ev3 (list: their ids).
+static int runLargePass(fmt_ctx* c, const fmt_kernels::MtDeviceBatch& db, uint32_t nEsc, std::vector<uint32_t>& list) {
+  const fmt_kernels::MtCaps big = fmt_kernels::mergeTreeCaps(true);
+  FMT_HIP(c, c->mtBigLeaves.reserve(static_cast<size_t>(nEsc) * big.leaves));
+  FMT_HIP(c, c->mtBigChars.reserve(static_cast<size_t>(nEsc) * big.chars));
+  FMT_HIP(c, c->mtBigProps.reserve(static_cast<size_t>(nEsc) * big.props));
+  if (c->mtPlan.anyAdjust) FMT_HIP(c, c->mtBigLegacy.reserve(static_cast<size_t>(nEsc) * big.leaves));
+  // every batch but a local one: a document the large tier is about to outgrow leaves a checkpoint
+  // for the huge tier (huge_ckpt.h) instead of failing; without the slab it restarts there from its
+  // first op
+  const bool hugeCk = c->mtRoute.largeHugeCkpt &&
+                      c->mtHugeCk.reserve(static_cast<size_t>(nEsc) * fmt_ckpt::kWords) == hipSuccess;
+  if (!hugeCk) (void)hipGetLastError();
+  FMT_HIP(c, hipEventRecord(c->ev2, c->stream));
+  FMT_HIP(c, fmt_kernels::launchMergeTreeLarge(db, mtOutView(c, true, hugeCk ? c->mtHugeCk.p : nullptr), c->mtRoute,
+                                               c->mtLists, nEsc, {c->numCUs, c->stream}));
+  FMT_HIP(c, hipEventRecord(c->ev3, c->stream));
+  c->timed2 = true;
+  list.resize(nEsc);
+  FMT_HIP(c, hipMemcpyAsync(list.data(), c->mtLists.toLarge + 1, nEsc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  for (uint32_t i = 0; i < nEsc; i++) c->mtBigSlot[list[i]] = static_cast<int32_t>(i);
+  return FMT_OK;
+}
+
+// Documents the large tier could not hold (FMT_E_CAPACITY: leaves, text, blocks, prop sets) replay
+// again in the huge tier, which has no such limit but device memory — the reference grows a tree
+// without bound (insertSegments, mergeTree.ts:1484-1517): from the checkpoint the large pass left
+// them at, or from their start. Not a local batch's (the huge tier lacks its records).
+static int growIntoHuge(fmt_ctx* c, const std::vector<uint32_t>& list) {
+  const uint32_t nEsc = static_cast<uint32_t>(list.size());
+  const fmt_kernels::MtCaps big = fmt_kernels::mergeTreeCaps(true);
+  std::vector<fmt_mt_doc_result> hb(nEsc);
+  std::vector<uint32_t> grow;
+  std::vector<int32_t> growSlot;  // the large-tier slot of a checkpointed document (-1: restart from op 0)
+  for (uint32_t i = 0; i < nEsc; i++) {
+    FMT_HIP(c, hipMemcpyAsync(&hb[i], c->mtHdr.p + list[i], sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
+  }
+  FMT_HIP(c, hipStreamSynchronize(c->stream));
+  for (uint32_t i = 0; i < nEsc; i++) {
+    if ((hb[i].status == FMT_E_CAPACITY || hb[i].status == fmt_ckpt::kStatusHuge) && c->mtHugeSlot[list[i]] < 0 &&
+        !c->mtRoute.largeLocal) {
+      grow.push_back(list[i]);
+      growSlot.push_back(hb[i].status == fmt_ckpt::kStatusHuge ? static_cast<int32_t>(i) : -1);
+    }
+  }
+  if (grow.empty()) return FMT_OK;
+  FMT_HIP(c, c->mtStartSegDev.reserve(grow.size()));
+  std::vector<fmt_mt_snapshot_seg> starts(grow.size());
+  for (size_t i = 0; i < grow.size(); i++) starts[i] = c->mtPlan.startSeg[grow[i]];
+  FMT_HIP(c, hipMemcpyAsync(c->mtStartSegDev.p, starts.data(), grow.size() * sizeof(fmt_mt_snapshot_seg),
+                            hipMemcpyHostToDevice, c->stream));
+  // (a document whose huge-tier state does not fit in device memory keeps the large tier's
+  // FMT_E_CAPACITY header)
+  for (size_t i = 0; i < grow.size(); i++) {
+    const uint32_t d = grow[i];
+    const uint64_t o0 = c->mtOffsHost[d], o1 = c->mtOffsHost[d + 1];
+    int rc;
+    if (c->mtSnapHost.size() > d && c->mtSnapHost[d].loaded) {
+      const fmt_mt_snapshot_doc& sd = c->mtSnapHost[d];
+      rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtSnapSegs.p + sd.first_seg, sd.n_header,
+                        sd.n_body, sd.min_seq, sd.seq, FMT_NON_COLLAB_CLIENT, 1024, c->mtPlan.docChars[d]);
+    } else {
+      rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtStartSegDev.p + i, starts[i].len > 0 ? 1 : 0,
+                        0, 0, 0, FMT_LOCAL_CLIENT, 1024, c->mtPlan.docChars[d]);
+    }
+    if (rc != FMT_OK && rc != FMT_E_CAPACITY) return rc;
+    if (growSlot[i] >= 0) {
+      if (rc == FMT_OK) {  // resume from the large tier's checkpoint and result slabs
+        const size_t k = static_cast<size_t>(growSlot[i]);
+        fmt_huge::HugeInputs& I = c->huge.back().in;
+        I.ck = c->mtHugeCk.p + k * fmt_ckpt::kWords;
+        I.ckLeaves = c->mtBigLeaves.p + k * big.leaves;
+        I.ckChars = c->mtBigChars.p + k * big.chars;
+        I.ckProps = c->mtBigProps.p + k * big.props;
+      } else {  // (no room in device memory: the document reports FMT_E_CAPACITY)
+        const int32_t st = FMT_E_CAPACITY;
+        FMT_HIP(c, hipMemcpyAsync(&c->mtHdr.p[d].status, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+        FMT_HIP(c, hipStreamSynchronize(c->stream));
+      }
+    }
+  }
+  const size_t ng = c->huge.size() - c->mtHugeLoaded;
+  if (ng > 0) {
+    const int rc = uploadHuge(c, c->mtHugeLoaded, c->hugeStates2, c->hugeInputs2, c->hugeOuts2);
+    if (rc != FMT_OK) return rc;
+    FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates2.p, c->hugeInputs2.p, c->hugeOuts2.p, static_cast<uint32_t>(ng),
+                                           c->mtPlan.anyAdjust, c->mtPlan.hasRmOrder(), c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  c->mtGrown = static_cast<uint32_t>(ng);
+  return FMT_OK;
+}
+
+
+int fmt_mt_run(fmt_ctx* c) {
+  if (c == nullptr || !c->mtLoaded) return setErr(c, FMT_E_USAGE, "fmt_mt_run before fmt_mt_load");
+  c->mtRan = false;  // (until this run completes: a device error half way leaves nothing to fetch)
+  invalidateReads(c);
+  FMT_HIP(c, hipSetDevice(c->device));
+  if (const int rc = releaseGrownHuge(c)) return rc;
+  const fmt_kernels::MtDeviceBatch db = mtBatchView(c);
+  if (const int rc = launchRegisterTiers(c, db)) return rc;
+  // Documents that overflowed the small tier replay again in the large tier: the host reads the list length.
   uint32_t nEsc = 0;
   c->mtGrown = 0;
-  FMT_HIP(c, hipMemcpyAsync(&nEsc, c->mtEsc.p, sizeof nEsc, hipMemcpyDeviceToHost, c->stream));
+  FMT_HIP(c, hipMemcpyAsync(&nEsc, c->mtLists.toLarge, sizeof nEsc, hipMemcpyDeviceToHost, c->stream));
   FMT_HIP(c, hipStreamSynchronize(c->stream));
   c->mtBigSlot.assign(c->mtDocs, -1);
   if (nEsc > 0) {
-    const fmt_kernels::MtCaps big = fmt_kernels::mergeTreeCaps(true);
-    FMT_HIP(c, c->mtBigLeaves.reserve(static_cast<size_t>(nEsc) * big.leaves));
-    FMT_HIP(c, c->mtBigChars.reserve(static_cast<size_t>(nEsc) * big.chars));
-    FMT_HIP(c, c->mtBigProps.reserve(static_cast<size_t>(nEsc) * big.props));
-    if (c->mtPlan.anyAdjust) FMT_HIP(c, c->mtBigLegacy.reserve(static_cast<size_t>(nEsc) * big.leaves));
-    // every batch but a local one: a document the large tier is about to outgrow leaves a checkpoint
-    // for the huge tier (huge_ckpt.h) instead of failing; without the slab it restarts there from its
-    // first op
-    const bool hugeCk = !c->mtPlan.local &&
-                        c->mtHugeCk.reserve(static_cast<size_t>(nEsc) * fmt_ckpt::kWords) == hipSuccess;
-    if (!hugeCk) (void)hipGetLastError();
-    fmt_kernels::MtDeviceOut bout{c->mtHdr.p, c->mtBigLeaves.p, c->mtBigChars.p, c->mtBigProps.p,
-                                  c->mtPlan.hasCatchup() ? c->mtCatchup.p : nullptr, c->mtPlan.hasRmOrder() ? c->mtRmOrder.p : nullptr,
-                                  c->mtPlan.obliterates && !c->mtPlan.hasRmOrder() && !c->mtPlan.anyAdjust && c->mtCkptOk ? c->mtCkpt.p : nullptr,
-                                  !c->mtPlan.hasRmOrder() ? c->mtLeaves.p : nullptr, !c->mtPlan.hasRmOrder() ? c->mtChars.p : nullptr,
-                                  c->mtPlan.anyAdjust ? c->mtBigLegacy.p : nullptr, hugeCk ? c->mtHugeCk.p : nullptr};
-    FMT_HIP(c, hipEventRecord(c->ev2, c->stream));
-    FMT_HIP(c, fmt_kernels::launchMergeTreeLarge(db, bout, c->mtEsc.p + 1, nEsc, c->numCUs, c->stream, c->mtPlan.obliterates,
-                                                 c->mtPlan.hasRmOrder(), c->mtSched.p + 2, c->mtPlan.anyAdjust, c->mtPlan.local));
-    FMT_HIP(c, hipEventRecord(c->ev3, c->stream));
-    c->timed2 = true;
-    std::vector<uint32_t> list(nEsc);
-    FMT_HIP(c, hipMemcpyAsync(list.data(), c->mtEsc.p + 1, nEsc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    FMT_HIP(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < nEsc; i++) c->mtBigSlot[list[i]] = static_cast<int32_t>(i);
-    // Documents the large tier could not hold (FMT_E_CAPACITY: leaves, text, blocks, prop sets)
-    // replay again from their start in the huge tier, which has no such limit but device memory —
-    // the reference grows a tree without bound (insertSegments, mergeTree.ts:1484-1517).
-    std::vector<fmt_mt_doc_result> hb(nEsc);
-    std::vector<uint32_t> grow;
-    std::vector<int32_t> growSlot;  // the large-tier slot of a checkpointed document (-1: restart from op 0)
-    for (uint32_t i = 0; i < nEsc; i++) {
-      FMT_HIP(c, hipMemcpyAsync(&hb[i], c->mtHdr.p + list[i], sizeof(fmt_mt_doc_result), hipMemcpyDeviceToHost, c->stream));
-    }
-    FMT_HIP(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < nEsc; i++) {
-      if ((hb[i].status == FMT_E_CAPACITY || hb[i].status == fmt_ckpt::kStatusHuge) && c->mtHugeSlot[list[i]] < 0 &&
-          !c->mtPlan.local) {
-        grow.push_back(list[i]);
-        growSlot.push_back(hb[i].status == fmt_ckpt::kStatusHuge ? static_cast<int32_t>(i) : -1);
-      }
-    }
-    if (!grow.empty()) {
-      FMT_HIP(c, c->mtStartSegDev.reserve(grow.size()));
-      std::vector<fmt_mt_snapshot_seg> starts(grow.size());
-      for (size_t i = 0; i < grow.size(); i++) starts[i] = c->mtPlan.startSeg[grow[i]];
-      FMT_HIP(c, hipMemcpyAsync(c->mtStartSegDev.p, starts.data(), grow.size() * sizeof(fmt_mt_snapshot_seg),
-                                hipMemcpyHostToDevice, c->stream));
-      // (a document whose huge-tier state does not fit in device memory keeps the large tier's
-      // FMT_E_CAPACITY header)
-      for (size_t i = 0; i < grow.size(); i++) {
-        const uint32_t d = grow[i];
-        const uint64_t o0 = c->mtOffsHost[d], o1 = c->mtOffsHost[d + 1];
-        int rc;
-        if (c->mtSnapHost.size() > d && c->mtSnapHost[d].loaded) {
-          const fmt_mt_snapshot_doc& sd = c->mtSnapHost[d];
-          rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtSnapSegs.p + sd.first_seg, sd.n_header,
-                            sd.n_body, sd.min_seq, sd.seq, FMT_NON_COLLAB_CLIENT, 1024, c->mtPlan.docChars[d]);
-        } else {
-          rc = setupHugeDoc(c, c->mtTextLen, c->mtNProps, d, o0, o1, c->mtStartSegDev.p + i, starts[i].len > 0 ? 1 : 0,
-                            0, 0, 0, FMT_LOCAL_CLIENT, 1024, c->mtPlan.docChars[d]);
-        }
-        if (rc != FMT_OK && rc != FMT_E_CAPACITY) return rc;
-        if (growSlot[i] >= 0) {
-          if (rc == FMT_OK) {  // resume from the large tier's checkpoint and result slabs
-            const size_t k = static_cast<size_t>(growSlot[i]);
-            fmt_huge::HugeInputs& I = c->huge.back().in;
-            I.ck = c->mtHugeCk.p + k * fmt_ckpt::kWords;
-            I.ckLeaves = c->mtBigLeaves.p + k * big.leaves;
-            I.ckChars = c->mtBigChars.p + k * big.chars;
-            I.ckProps = c->mtBigProps.p + k * big.props;
-          } else {  // (no room in device memory: the document reports FMT_E_CAPACITY)
-            const int32_t st = FMT_E_CAPACITY;
-            FMT_HIP(c, hipMemcpyAsync(&c->mtHdr.p[d].status, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
-            FMT_HIP(c, hipStreamSynchronize(c->stream));
-          }
-        }
-      }
-      const size_t ng = c->huge.size() - c->mtHugeLoaded;
-      if (ng > 0) {
-        const int rc = uploadHuge(c, c->mtHugeLoaded, c->hugeStates2, c->hugeInputs2, c->hugeOuts2);
-        if (rc != FMT_OK) return rc;
-        FMT_HIP(c, fmt_kernels::launchHugeDocs(c->hugeStates2.p, c->hugeInputs2.p, c->hugeOuts2.p, static_cast<uint32_t>(ng),
-                                               c->mtPlan.anyAdjust, c->mtPlan.hasRmOrder(), c->stream));
-        FMT_HIP(c, hipStreamSynchronize(c->stream));
-      }
-      c->mtGrown = static_cast<uint32_t>(ng);
-    }
+    std::vector<uint32_t> list;
+    if (const int rc = runLargePass(c, db, nEsc, list)) return rc;
+    if (const int rc = growIntoHuge(c, list)) return rc;
   }
   c->timed = true;
   c->stats = fmt_stats{};
@@ -1812,9 +1835,7 @@ int fmt_mt_run(fmt_ctx* c) {
   c->stats.bytes_read = c->mtNOps * sizeof(fmt_mt_op) + (c->mtPlan.insertChars + c->mtPlan.initChars) * 2 +
                         (c->mtDocs + 1ull) * sizeof(uint64_t);
   c->stats.bytes_written = static_cast<uint64_t>(c->mtDocs) * sizeof(fmt_mt_doc_result);
-  // compact + small tier (no remove-order recording) or small tier alone, then the large tier when it ran
-  // (+1: the huge-tier pass over documents that outgrew the large tier, after the timed events)
-  c->stats.launches = (!c->mtPlan.hasRmOrder() ? 2 : 1) + (nEsc > 0 ? 1 : 0) + (c->mtGrown > 0 ? 1 : 0);
+  c->stats.launches = c->mtRoute.nominalLaunches(nEsc > 0, c->mtGrown > 0);
   c->mtRan = true;
   return FMT_OK;
 }
@@ -2801,6 +2822,25 @@ int fmt_internal_mt_plan(const fmt_mt_batch* b, const char** err, const uint64_t
     for (int64_t x : {int64_t{P.refused[i]}, int64_t{h.status}, int64_t{h.fail_seq}, int64_t{h.cur_seq}, int64_t{h.min_seq}})
       w.push_back(static_cast<uint64_t>(x));
   }
+  *out = w.data();
+  *nWords = w.size();
+  return rc;
+}
+
+// Test hook (not part of fmt.h): the route fmt_mt_load plans for `b` with or without the checkpoint and step-down
+// slabs, as mt_route_words.h lays it out; no device needed. rounds <= 0 / local_path < 0: this build's. Returns the
+// plan's status (refused: *err says why, no words). Valid until the calling thread's next call.
+int fmt_internal_mt_route(const fmt_mt_batch* b, int ckptSlab, int descSlab, int rounds, int localPath, const char** err,
+                          const uint32_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint32_t> w;
+  fmt_plan::MtPlan P;
+  if (err == nullptr || out == nullptr || nWords == nullptr || rounds > fmt_plan::kMaxDescendRounds) return FMT_E_USAGE;
+  *err = nullptr;
+  const int rc = fmt_plan::planMergeTreeLoad(b, fmt_kernels::mergeTreeCaps(true), P, err);
+  w.clear();
+  if (rc == FMT_OK)
+    w = fmt_plan::routeWords(fmt_plan::planRoute(P, ckptSlab != 0, descSlab != 0, rounds > 0 ? rounds : fmt_plan::kDescendRounds,
+                                                 localPath >= 0 ? localPath : FMT_LOCAL_PATH));
   *out = w.data();
   *nWords = w.size();
   return rc;

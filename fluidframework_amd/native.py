@@ -481,6 +481,63 @@ def mt_plan(batch, struct=None) -> MtPlanResult:
     return r
 
 
+MT_TIERS = ("micro", "compact", "small", "large")  # csrc/mt_route.h MtTier
+MT_LIST_KINDS = ("none", "every", "caller", "microUp", "compactUp", "toLarge", "ordered", "round")  # MtListKind
+MT_DEAL_KINDS = ("compact", "small", "large", "micro", "round")  # MtDealKind
+
+
+def mt_variant_key(ob=False, rm=False, adj=False, loc=False) -> int:
+    """csrc/mt_route.h MtVariant::key"""
+    return int(ob) | int(rm) << 1 | int(adj) << 2 | int(loc) << 3
+
+
+class MtRouteResult:
+    """A route read back (csrc/mt_route.h routeWords): the five out-slab booleans (`tiers_ckpt`, `large_ckpt`,
+    `large_resumes_small`, `large_huge_ckpt`, `large_local`), `large` (the large pass's variant key), `rounds`,
+    `nominal_launches` ({(large_ran, grew): launches}), `steps` (dicts: tier, variant, in / up / down /
+    order_into as names with "round(r,k)" for the step-down lists, deal likewise, descend) and `kernels`
+    (the (tier, variant key) pairs that exist as kernels)."""
+
+
+def parse_mt_route(words) -> MtRouteResult:
+    w = [int(x) for x in words]
+    r = MtRouteResult()
+    r.tiers_ckpt, r.large_ckpt, r.large_resumes_small, r.large_huge_ckpt, r.large_local = (bool(x) for x in w[:5])
+    r.large, r.rounds = w[5], w[6]
+    r.nominal_launches = {(False, False): w[7], (True, False): w[8], (False, True): w[9], (True, True): w[10]}
+
+    def name(kinds, kind, rr, k):
+        return f"round({rr},{k})" if kinds[kind] == "round" else kinds[kind]
+
+    at, r.steps = 12, []
+    for _ in range(w[11]):
+        s = w[at:at + 16]
+        r.steps.append({"tier": MT_TIERS[s[0]], "variant": s[1], "in": name(MT_LIST_KINDS, *s[2:5]),
+                        "up": name(MT_LIST_KINDS, *s[5:8]), "down": name(MT_LIST_KINDS, *s[8:11]),
+                        "order_into": MT_LIST_KINDS[s[11]], "deal": name(MT_DEAL_KINDS, *s[12:15]), "descend": bool(s[15])})
+        at += 16
+    r.kernels = {(MT_TIERS[w[at + 1 + 2 * i]], w[at + 2 + 2 * i]) for i in range(w[at])}
+    assert at + 1 + 2 * w[at] == len(w)
+    return r
+
+
+def mt_route(batch, ckpt_slab=True, desc_slab=True, rounds=0, local_path=-1, struct=None) -> MtRouteResult:
+    """fmt_internal_mt_route: the route fmt_mt_load plans for `batch` when the checkpoint / step-down slabs
+    are (not) allocated, no device needed. rounds / local_path: other than the build's. Raises EngineError
+    for a batch fmt_mt_load refuses."""
+    b, keep = (struct, None) if struct is not None else batch_struct(batch)
+    P = ctypes.c_void_p
+    f = lib().fmt_internal_mt_route
+    f.argtypes = [ctypes.POINTER(FmtMtBatch)] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(P),
+                                                                     ctypes.POINTER(ctypes.c_uint64)]
+    err, out, n = ctypes.c_char_p(), P(), ctypes.c_uint64()
+    rc = f(ctypes.byref(b), int(ckpt_slab), int(desc_slab), rounds, local_path, ctypes.byref(err), ctypes.byref(out),
+           ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, err.value.decode() if err.value else "fmt_internal_mt_route")
+    return parse_mt_route(np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint32)), (n.value,)).copy())
+
+
 MT_VALUE_COMPUTED = 0x8000  # fmt.h FMT_MT_VALUE_COMPUTED: value ids at or above it index the document's numbers
 
 

@@ -1,16 +1,17 @@
 """The plain-batch cascade with stepping down under host emulation (tests/emu/mt_emu_tiers.cpp through
-micro_cascade.lib(): one launch per call, the step-down switch and both lists exposed), the rounds of
-launchMergeTree (csrc/mergetree.hip) driven from here, and the documents the step-down tests are built
+micro_cascade.lib(): one launch per call, the step-down switch and both lists exposed), the steps of the
+route launchMergeTree walks (csrc/mt_route.h) run from here, and the documents the step-down tests are built
 from. Shared by test_descend_emulated.py (CPU) and test_gpu_descend.py (the same batches on the device)."""
 import ctypes
 
 import numpy as np
 
 from fluidframework_amd.native import batch_struct
-from micro_cascade import CKPT, COMPACT, E_CAPACITY, LARGE, MICRO, SMALL, Cascade, _msg, lib
+from micro_cascade import CKPT, COMPACT, E_CAPACITY, LARGE, MICRO, SMALL, Cascade, _msg, lib, route
 from mt_compare import _p
 
-ROUNDS = 2  # csrc/mergetree.hip kDescendRounds
+ROUNDS = int(lib().emu_descend_rounds())  # csrc/mt_route.h kDescendRounds
+TIERS = {"micro": MICRO, "compact": COMPACT, "small": SMALL, "large": LARGE}
 
 
 def consts():
@@ -91,20 +92,19 @@ class DescendCascade(Cascade):
             self.hops[ids] += 1
         return st
 
-    def rounds(self, rounds=ROUNDS, descend=True):
-        """launchMergeTree's plain cascade. Returns the list of the documents left for the large tier."""
-        esc = self.new_list()
-        to_compact, to_small = self.new_list(), self.new_list()
-        self.launch(MICRO, None, False, up=to_compact)
-        for r in range(rounds):
-            on = descend and r + 1 < rounds and self.ck is not None
-            nxt_compact = self.new_list() if on else None
-            self.launch(COMPACT, to_compact, on, up=to_small)
-            self.launch(SMALL, to_small, on, up=esc, down=nxt_compact)
-            if not on:
-                break
-            to_compact, to_small = nxt_compact, self.new_list()
-        return esc
+    def rounds(self, rounds=0, descend=True, docs=None):
+        """The register tiers of the route the runtime plans for the batch (csrc/mt_route.h planRoute, read
+        through micro_cascade.route), step by step as launchMergeTree walks it; a step's reordering of its
+        list is left out (no result depends on list order). rounds: other than the build's; descend False: no
+        step-down slab; docs: the caller's list. Returns the list of the documents left for the large tier."""
+        program = route(self.batch, ckpt_slab=self.ck is not None, desc_slab=descend, rounds=rounds)
+        lists = {"none": None, "every": None, "caller": docs}
+        for s in program.steps:
+            assert s["variant"] == 0 and (s["in"] != "caller" or s["tier"] == "micro"), s  # (micro resumes nothing)
+            src, up, down = (lists[k] if k in lists else lists.setdefault(k, self.new_list())
+                             for k in (s["in"], s["up"], s["down"]))
+            self.launch(TIERS[s["tier"]], src, s["descend"], up=up, down=down)
+        return lists["toLarge"]
 
 
 def held_by_last_round(batch, rounds=ROUNDS):

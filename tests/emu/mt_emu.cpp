@@ -2,14 +2,11 @@
 // binding around it (mt_bind.h) compiled for the host with the 64-lane emulation of wave.h, so the CPU
 // parity suite can check the exact kernel logic against the oracle without a GPU. Never loaded by the
 // product (libfmt.so has no CPU path).
-#include <algorithm>
 #include <cstring>
-#include <memory>
-#include <type_traits>
 #include <vector>
 
-#include "emu_batch.h"
-#include "../../fluidframework_amd/csrc/mt_plan.h"
+#define EMU_ROUTE_ALL_VARIANTS 1
+#include "emu_route.h"
 
 // Annotate-adjust state of the last emulated replay (the runtime's number slabs, fixed capacity
 // here): the batch's host numbers sorted for number → id lookups, per-document number tables.
@@ -96,175 +93,94 @@ static void prepareLocal(uint32_t nDocs) {
                               g_lscratch.data(), g_lscratchOffs.data()};
 }
 
-template <bool Ob, class C, bool Rm = false, bool Adj = false, bool Loc = false>
-static int replayAll(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                     fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
-                     fmt_mt_remove_order* rmOrder, uint32_t capRm, uint32_t* ckpt = nullptr,
-                     bool onlyEscalated = false, size_t leafStride = 0, size_t charStride = 0,
-                     const fmt_mt_leaf* smallLeaves = nullptr, const uint16_t* smallChars = nullptr,
-                     uint16_t* legacy = nullptr, uint32_t* hugeCk = nullptr) {
-  using Doc = fmt_mt::Doc<Ob, C, Rm, Adj, Loc>;
-  auto scratch = std::make_unique<fmt_mt::Scratch<C>>();
-  auto doc = std::make_unique<Doc>();
-  const EmuBatch eb(b, catchup != nullptr, capCatchup, rmOrder != nullptr, capRm, g_nums.empty() ? nullptr : &g_adj,
-                    Loc ? &g_loc : nullptr);
-  const fmt_kernels::MtDeviceOut out{headers, leaves, chars, props, catchup, rmOrder, ckpt, smallLeaves, smallChars,
-                                     legacy, hugeCk};
-  if (leafStride == 0) leafStride = Doc::kCapLeaves;  // the tier alone, at its own strides
-  if (charStride == 0) charStride = Doc::kCapChars;
-  int status = FMT_OK;
-  for (uint32_t d = 0; d < b->n_docs; d++) {
-    if (onlyEscalated && headers[d].status != FMT_E_CAPACITY && headers[d].status != fmt_mt::kCkptEscalate) continue;
-    std::memset(scratch.get(), 0xCD, sizeof(fmt_mt::Scratch<C>));  // poison: state must be initialized
-    // (onlyEscalated: what a launch over the overflow list replays)
-    const fmt_kernels::DocBinding bd =
-        fmt_kernels::bindDoc<Doc>(eb.view, out, d, d, leafStride, charStride, Doc::kPropCap, onlyEscalated);
-    new (doc.get()) Doc();
-    doc->s = scratch.get();
-    doc->run(bd.in, bd.o);
-    (void)fmt_kernels::collectHeader(headers[d]);  // (kCapacityFinal → FMT_E_CAPACITY; no lists here)
-    if (headers[d].status == fmt_mt::kCkptEscalate) continue;  // the small tier resumes it
-    if (headers[d].status == fmt_ckpt::kStatusHuge) continue;  // the huge tier resumes it
-    if (headers[d].status != FMT_OK && status == FMT_OK) status = headers[d].status;
+namespace {
+
+using fmt_kernels::MtDeviceOut;
+using fmt_kernels::Slab;
+using fmt_plan::MtRoute;
+using fmt_plan::MtTier;
+using fmt_plan::MtVariant;
+using S = fmt_mt::SmallTier;
+using G = fmt_mt::LargeTier;
+
+// The caller's arrays of one replay call: results (at the strides the entry point documents) and record slabs.
+struct Call {
+  const fmt_mt_batch* b;
+  fmt_mt_doc_result* headers;
+  fmt_mt_leaf* leaves;
+  uint16_t* chars;
+  fmt_mt_propset* props;
+  fmt_mt_catchup_range* catchup = nullptr;
+  uint32_t capCatchup = 0;
+  fmt_mt_remove_order* rmOrder = nullptr;
+  uint32_t capRm = 0;
+  uint32_t* hugeCk = nullptr;
+  EmuBatch batch(bool loc) const {
+    return EmuBatch(b, catchup != nullptr, capCatchup, rmOrder != nullptr, capRm, g_nums.empty() ? nullptr : &g_adj, loc ? &g_loc : nullptr);
   }
-  return status;
+};
+
+// Annotate-adjust batches: the legacy getAtSeq views of the call (emu_mt_legacy_props) at `stride`.
+uint16_t* legacyViews(const Call& c, bool adj, size_t stride) {
+  if (!adj) return nullptr;
+  g_legacyStride = stride;
+  g_legacy.assign(c.b->n_docs * stride, 0xFFFFu);
+  return g_legacy.data();
 }
 
-// The runtime's compact → small cascade with checkpoints (results at small-tier strides).
-template <bool Ob>
-static int cascadeCompactSmall(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                               fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
-                               fmt_mt_remove_order* rmOrder, uint32_t capRm) {
-  using S = fmt_mt::SmallTier;
-  using D = fmt_mt::Doc<Ob, fmt_mt::CompactTier>;
-  std::unique_ptr<uint32_t[]> ck(new uint32_t[static_cast<size_t>(b->n_docs) * D::kCkptWords]);
-  const size_t stride = fmt_mt::Doc<Ob, S>::kCapLeaves;
-  replayAll<Ob, fmt_mt::CompactTier>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, ck.get(),
-                                     false, stride, S::kCapChars);
-  return replayAll<Ob, S>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, ck.get(), true);
+// One tier alone over every document from its first op, at its own strides, without checkpoints (the large
+// tier of an annotate-adjust batch: with the legacy views).
+int oneTier(const Call& c, MtTier tier, MtVariant v) {
+  const EmuBatch eb = c.batch(v.loc);
+  const MtDeviceOut out{c.headers, c.leaves, c.chars, c.props, c.catchup, c.rmOrder, nullptr, nullptr, nullptr,
+                        legacyViews(c, v.adj && tier == MtTier::kLarge, Slab<G>::kLeaves), c.hugeCk};
+  int failed = FMT_OK;
+  return emu::replayStep(tier, v, emu::Launch{eb, out, nullptr, false, nullptr, nullptr, true, &failed}) < 0 ? FMT_E_UNSUPPORTED : failed;
 }
 
-// The whole cascade: compact → small → large with both checkpoints (results at large-tier strides).
-template <bool Ob>
-static int fullCascade(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                       fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
-                       fmt_mt_remove_order* rmOrder, uint32_t capRm) {
-  using S = fmt_mt::SmallTier;
-  using G = fmt_mt::LargeTier;
-  using D = fmt_mt::Doc<Ob, fmt_mt::CompactTier>;
-  using DS = fmt_mt::Doc<Ob, S>;
-  using DL = fmt_mt::Doc<Ob, G>;
-  const size_t n = b->n_docs;
-  std::unique_ptr<uint32_t[]> ck(new uint32_t[n * D::kCkptWords]);
-  std::unique_ptr<fmt_mt_leaf[]> sl(new fmt_mt_leaf[n * DS::kCapLeaves]);
-  std::unique_ptr<uint16_t[]> sc(new uint16_t[n * S::kCapChars]);
-  std::unique_ptr<fmt_mt_propset[]> sp(new fmt_mt_propset[n * S::kPropCap]);
-  replayAll<Ob, fmt_mt::CompactTier>(b, headers, sl.get(), sc.get(), sp.get(), catchup, capCatchup, rmOrder, capRm,
-                                     ck.get(), false, DS::kCapLeaves, S::kCapChars);
-  replayAll<Ob, S>(b, headers, sl.get(), sc.get(), sp.get(), catchup, capCatchup, rmOrder, capRm, ck.get(), true);
+// The route as fmt_mt_run runs it: its register tiers with the checkpoint slab (small-tier strides) and,
+// withLarge, the large pass with the views the route's booleans name (large strides, every document).
+int cascade(const Call& c, const MtRoute& R, bool withLarge) {
+  const size_t n = c.b->n_docs, SL = Slab<S>::kLeaves, SC = Slab<S>::kChars, SP = Slab<S>::kProps;
+  const bool adj = R.large.adj;
+  const EmuBatch eb = c.batch(R.large.loc);
+  std::vector<uint32_t> ck(n * fmt_mt::Doc<false, fmt_mt::CompactTier>::kCkptWords), toLarge(n + 1);
+  std::vector<fmt_mt_leaf> sl(withLarge ? n * SL : 0);
+  std::vector<uint16_t> sc(withLarge ? n * SC : 0), smallLegacy(withLarge && adj ? n * SL : 0, 0xFFFFu);
+  std::vector<fmt_mt_propset> sp(withLarge ? n * SP : 0);
+  fmt_mt_leaf* tl = withLarge ? sl.data() : c.leaves;
+  uint16_t* tc = withLarge ? sc.data() : c.chars;
+  fmt_mt_propset* tp = withLarge ? sp.data() : c.props;
+  uint16_t* legacy = legacyViews(c, adj, withLarge ? Slab<G>::kLeaves : SL);
+  const MtDeviceOut tiers{c.headers, tl, tc, tp, c.catchup, c.rmOrder, R.tiersCkpt ? ck.data() : nullptr, nullptr, nullptr,
+                          withLarge && adj ? smallLegacy.data() : legacy};
+  int failed = FMT_OK;
+  if (emu::runRoute(R, eb, tiers, toLarge.data(), &failed) < 0) return FMT_E_UNSUPPORTED;
+  if (!withLarge) return failed;
+  std::vector<uint8_t> up(n, 0);
+  for (uint32_t i = 0; i < toLarge[0]; i++) up[toLarge[1 + i]] = 1;
   for (size_t d = 0; d < n; d++) {  // documents done below the large tier: results to the large strides
-    const fmt_mt_doc_result& h = headers[d];
-    if (h.status == FMT_E_CAPACITY || h.status == fmt_mt::kCkptEscalate) continue;
-    std::memcpy(leaves + d * DL::kCapLeaves, sl.get() + d * DS::kCapLeaves, h.n_leaves * sizeof(fmt_mt_leaf));
-    std::memcpy(chars + d * G::kCapChars, sc.get() + d * S::kCapChars, h.n_chars * sizeof(uint16_t));
-    std::memcpy(props + d * G::kPropCap, sp.get() + d * S::kPropCap, h.n_props * sizeof(fmt_mt_propset));
+    const fmt_mt_doc_result& h = c.headers[d];
+    if (up[d]) continue;
+    std::memcpy(c.leaves + d * Slab<G>::kLeaves, tl + d * SL, h.n_leaves * sizeof(fmt_mt_leaf));
+    std::memcpy(c.chars + d * Slab<G>::kChars, tc + d * SC, h.n_chars * sizeof(uint16_t));
+    std::memcpy(c.props + d * Slab<G>::kProps, tp + d * SP, h.n_props * sizeof(fmt_mt_propset));
+    if (adj) std::memcpy(legacy + d * Slab<G>::kLeaves, smallLegacy.data() + d * SL, h.n_leaves * sizeof(uint16_t));
   }
-  // (the large tier reads the live-obliterate table from the checkpoint slots, Ob only)
-  return replayAll<Ob, G>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, Ob ? ck.get() : nullptr,
-                          true, 0, 0, sl.get(), sc.get());
+  const MtDeviceOut large{c.headers, c.leaves, c.chars, c.props, c.catchup, c.rmOrder, R.largeCkpt ? ck.data() : nullptr,
+                          R.largeResumesSmall ? tl : nullptr, R.largeResumesSmall ? tc : nullptr, legacy};
+  const emu::Launch pass{eb, large, toLarge.data(), true, nullptr, nullptr, false, &failed};
+  return emu::replayStep(MtTier::kLarge, R.large, pass) < 0 ? FMT_E_UNSUPPORTED : failed;
 }
 
-// Batches with annotate-adjust: the small tier (Doc<true, S, Rm, true>) over every document; with
-// large, documents it cannot hold replay again from their first op in the large tier (results at
-// large strides), as the runtime runs them.
-static int adjustCascade(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                         fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
-                         fmt_mt_remove_order* rmOrder, uint32_t capRm, int large, bool rm) {
-  using S = fmt_mt::SmallTier;
-  using G = fmt_mt::LargeTier;
-  if (large == 0 || large == 3) {
-    g_legacyStride = fmt_mt::Doc<true, S>::kCapLeaves;
-    g_legacy.assign(b->n_docs * g_legacyStride, 0xFFFFu);
-    return rm ? replayAll<true, S, true, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm,
-                                               nullptr, false, 0, 0, nullptr, nullptr, g_legacy.data())
-              : replayAll<true, S, false, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm,
-                                                nullptr, false, 0, 0, nullptr, nullptr, g_legacy.data());
-  }
-  using DS = fmt_mt::Doc<true, S, false, true>;
-  using DL = fmt_mt::Doc<true, G, false, true>;
-  const size_t n = b->n_docs;
-  std::unique_ptr<fmt_mt_leaf[]> sl(new fmt_mt_leaf[n * DS::kCapLeaves]);
-  std::unique_ptr<uint16_t[]> sc(new uint16_t[n * S::kCapChars]);
-  std::unique_ptr<fmt_mt_propset[]> sp(new fmt_mt_propset[n * S::kPropCap]);
-  std::vector<uint16_t> smallLegacy(n * DS::kCapLeaves, 0xFFFFu);
-  if (rm) replayAll<true, S, true, true>(b, headers, sl.get(), sc.get(), sp.get(), catchup, capCatchup, rmOrder, capRm,
-                                         nullptr, false, 0, 0, nullptr, nullptr, smallLegacy.data());
-  else replayAll<true, S, false, true>(b, headers, sl.get(), sc.get(), sp.get(), catchup, capCatchup, rmOrder, capRm,
-                                       nullptr, false, 0, 0, nullptr, nullptr, smallLegacy.data());
-  g_legacyStride = DL::kCapLeaves;
-  g_legacy.assign(n * g_legacyStride, 0xFFFFu);
-  for (size_t d = 0; d < n; d++) {
-    const fmt_mt_doc_result& h = headers[d];
-    if (h.status == FMT_E_CAPACITY) continue;
-    std::memcpy(leaves + d * DL::kCapLeaves, sl.get() + d * DS::kCapLeaves, h.n_leaves * sizeof(fmt_mt_leaf));
-    std::memcpy(chars + d * G::kCapChars, sc.get() + d * S::kCapChars, h.n_chars * sizeof(uint16_t));
-    std::memcpy(props + d * G::kPropCap, sp.get() + d * S::kPropCap, h.n_props * sizeof(fmt_mt_propset));
-    std::memcpy(g_legacy.data() + d * DL::kCapLeaves, smallLegacy.data() + d * DS::kCapLeaves, h.n_leaves * sizeof(uint16_t));
-  }
-  return rm ? replayAll<true, G, true, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, nullptr,
-                                             true, 0, 0, nullptr, nullptr, g_legacy.data())
-            : replayAll<true, G, false, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, nullptr,
-                                              true, 0, 0, nullptr, nullptr, g_legacy.data());
-}
-
-template <bool Adj>
-static int replayLocal(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
-                       fmt_mt_propset* props, int largeOnly) {
-  using G = fmt_mt::LargeTier;
-  using K = fmt_mt::CompactTier;
-  using S = fmt_mt::SmallTier;
-  using DS = fmt_mt::Doc<false, S>;
-  using DL = fmt_mt::Doc<false, G, false, Adj, true>;
-  const size_t n = b->n_docs;
-  // (annotate-adjust batches: the legacy getAtSeq views, emu_mt_legacy_props, at large strides)
-  std::vector<uint16_t> smallLegacy(Adj ? n * DS::kCapLeaves : 0, 0xFFFFu);
-  if (Adj) {
-    g_legacyStride = DL::kCapLeaves;
-    g_legacy.assign(n * g_legacyStride, 0xFFFFu);
-  }
-  if (largeOnly == 1)
-    return replayAll<false, G, false, Adj, true>(b, headers, leaves, chars, props, nullptr, 0, nullptr, 0, nullptr, false, 0,
-                                                 0, nullptr, nullptr, Adj ? g_legacy.data() : nullptr);
-  std::unique_ptr<fmt_mt_leaf[]> sl(new fmt_mt_leaf[n * DS::kCapLeaves]);
-  std::unique_ptr<uint16_t[]> sc(new uint16_t[n * S::kCapChars]);
-  std::unique_ptr<fmt_mt_propset[]> sp(new fmt_mt_propset[n * S::kPropCap]);
-  if (largeOnly == 2 || largeOnly == 3)
-    replayAll<false, K, false, Adj, true>(b, headers, sl.get(), sc.get(), sp.get(), nullptr, 0, nullptr, 0, nullptr, false,
-                                          DS::kCapLeaves, S::kCapChars, nullptr, nullptr,
-                                          Adj ? smallLegacy.data() : nullptr);
-  if (largeOnly == 2) return FMT_OK;  // (diagnostics: the compact tier's statuses alone)
-  // the small tier's local variant over the documents the compact tier could not hold (from op 0);
-  // mode 0 (the runtime's default, mergetree_local.hip FMT_LOCAL_PATH 1) starts here with every document
-  replayAll<false, S, false, Adj, true>(b, headers, sl.get(), sc.get(), sp.get(), nullptr, 0, nullptr, 0, nullptr,
-                                        largeOnly == 3, 0, 0, nullptr, nullptr, Adj ? smallLegacy.data() : nullptr);
-  for (size_t d = 0; d < n; d++) {  // documents done below the large tier: results to the large strides
-    const fmt_mt_doc_result& h = headers[d];
-    if (h.status == FMT_E_CAPACITY) continue;
-    std::memcpy(leaves + d * DL::kCapLeaves, sl.get() + d * DS::kCapLeaves, h.n_leaves * sizeof(fmt_mt_leaf));
-    std::memcpy(chars + d * G::kCapChars, sc.get() + d * S::kCapChars, h.n_chars * sizeof(uint16_t));
-    std::memcpy(props + d * G::kPropCap, sp.get() + d * S::kPropCap, h.n_props * sizeof(fmt_mt_propset));
-    if (Adj) std::memcpy(g_legacy.data() + d * DL::kCapLeaves, smallLegacy.data() + d * DS::kCapLeaves, h.n_leaves * sizeof(uint16_t));
-  }
-  return replayAll<false, G, false, Adj, true>(b, headers, leaves, chars, props, nullptr, 0, nullptr, 0, nullptr, true, 0, 0,
-                                               nullptr, nullptr, Adj ? g_legacy.data() : nullptr);
-}
+}  // namespace
 
 extern "C" {
 
 // large = 0: the small tier (registers + LDS text); 1: the large tier (HBM text) that the runtime
-// replays overflowing documents in; 2: the compact tier (4 register rows) plain batches start in;
-// 3: the compact → small cascade with checkpoints (small-tier strides); 4: the whole compact → small
-// → large cascade (large-tier strides).
+// replays overflowing documents in; 2: the compact tier (4 register rows); 3: the register tiers of the
+// batch's route with checkpoints (small-tier strides); 4: the whole route, register tiers and the large
+// pass (large-tier strides).
 int emu_mt_capacity(int large, uint32_t* leaves, uint32_t* chars, uint32_t* props) {
   if (large == 3) large = 0;
   if (large == 4) large = 1;
@@ -284,108 +200,63 @@ int emu_mt_capacity(int large, uint32_t* leaves, uint32_t* chars, uint32_t* prop
   return 0;
 }
 
-// Same strides as the GPU result buffers of the tier (kCapLeaves / kCapChars / kPropCap per
-// document). Like the runtime, batches holding obliterates run the Doc<true> variant (or always,
-// with forceOb).
+// Same strides as the GPU result buffers of the tier. The flags are the plan's (mt_plan.h; forceOb: the
+// obliterate variants whatever the ops hold), the variants the route's (mt_route.h). 3 and 4 execute the route;
+// 0, 1 and 2 are one tier of it alone over every document from its first op. An annotate-adjust batch's route
+// is the small tier, then the large pass: 0 and 3 are its register tier, anything else the whole of it.
 int emu_mt_replay(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
                   fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup, int forceOb, int large,
                   fmt_mt_remove_order* rmOrder, uint32_t capRm) {
   prepareNumbers(b);
   g_legacyStride = 0;
-  if (b->adjusts != nullptr) {  // the runtime's annotate-adjust path: Adj variants, no checkpoints
-    bool rmA = false;
-    for (uint64_t i = 0; i < b->n_ops && !rmA; i++) rmA = (b->ops[i].flags & FMT_MT_F_RMORDER) != 0;
-    return adjustCascade(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, large, rmA);
-  }
-  bool ob = forceOb != 0;
-  for (uint64_t i = 0; i < b->n_ops && !ob; i++) ob = b->ops[i].type == FMT_MT_OBLITERATE || b->ops[i].type == FMT_MT_OBLITERATE_SIDED;
-  using S = fmt_mt::SmallTier;
-  using G = fmt_mt::LargeTier;
-  bool rm = false;
-  for (uint64_t i = 0; i < b->n_ops && !rm; i++) rm = (b->ops[i].flags & FMT_MT_F_RMORDER) != 0;
-  if (large == 2 && !rm)
-    return ob ? replayAll<true, fmt_mt::CompactTier>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm)
-              : replayAll<false, fmt_mt::CompactTier>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  if (large == 4 && !rm)  // the whole cascade: compact → small → large, results at large strides
-    return ob ? fullCascade<true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm)
-              : fullCascade<false>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  if (large == 3 && !rm)  // the runtime's cascade: compact tier with checkpoints, then the small tier
-    return ob ? cascadeCompactSmall<true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm)
-              : cascadeCompactSmall<false>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  if (large == 1) {
-    if (ob && rm) return replayAll<true, G, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-    if (ob) return replayAll<true, G>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-    if (rm) return replayAll<false, G, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-    return replayAll<false, G>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  }
-  if (ob && rm) return replayAll<true, S, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  if (ob) return replayAll<true, S>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  if (rm) return replayAll<false, S, true>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
-  return replayAll<false, S>(b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm);
+  MtRoute R;
+  if (const int rc = emu::planRouteOf(b, true, true, 0, -1, R, MtVariant{forceOb != 0, false, false, false})) return rc;
+  const Call c{b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm};
+  const MtVariant v = R.large;  // (the small tier's variant where it is a batch's first tier is the large pass's)
+  if (v.adj ? large != 0 && large != 3 : large == 4) return cascade(c, R, true);
+  if (v.adj || large == 3) return cascade(c, R, false);
+  if (large == 1) return oneTier(c, MtTier::kLarge, v);
+  if (large == 2 && !v.rm) return oneTier(c, MtTier::kCompact, MtVariant{v.ob, false, false, false});
+  return oneTier(c, MtTier::kSmall, v);
 }
 
 // The large tier over every document from its first op, each document it is about to outgrow
 // stopping with its large → huge checkpoint (hugeCk: fmt_ckpt::kWords words per document; header
-// status fmt_ckpt::kStatusHuge) for emu_huge_resume (results at large strides), for any flag set the
-// runtime accepts (launchMergeTreeLarge's choice of variant): annotate-adjust batches run
-// Doc<true, G, Rm, true>, others Doc<Ob, G, Rm>, with Rm when the batch holds FMT_MT_F_RMORDER ops
-// (rmOrder[n_docs x capRm] then receives the entries, which keep their leaf ids in a stopped document)
-// and catch-up recording beside either (catchup[n_docs x capCatchup], or nullptr). Annotate-adjust
-// batches: the legacy views of the documents the large tier finishes via emu_mt_legacy_props, and each
-// document's PropertiesManager records and computed numbers, which the huge tier resumes with, via
-// emu_mt_adj_slab.
+// status fmt_ckpt::kStatusHuge) for emu_huge_resume (results at large strides), in the route's large
+// variant. With FMT_MT_F_RMORDER ops rmOrder[n_docs x capRm] receives the entries, which keep their leaf
+// ids in a stopped document; catchup[n_docs x capCatchup] or nullptr. Annotate-adjust batches: the legacy
+// views via emu_mt_legacy_props, the PropertiesManager records and computed numbers via emu_mt_adj_slab.
 int emu_mt_replay_large_ckpt(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
                              fmt_mt_propset* props, fmt_mt_catchup_range* catchup, uint32_t capCatchup,
                              fmt_mt_remove_order* rmOrder, uint32_t capRm, uint32_t* hugeCk) {
-  using G = fmt_mt::LargeTier;
   g_nums.clear();
   g_legacyStride = 0;
-  bool ob = false, rm = false;
-  for (uint64_t i = 0; i < b->n_ops; i++) {
-    ob = ob || b->ops[i].type == FMT_MT_OBLITERATE || b->ops[i].type == FMT_MT_OBLITERATE_SIDED;
-    rm = rm || (b->ops[i].flags & FMT_MT_F_RMORDER) != 0;
-  }
-  if (rm && rmOrder == nullptr) return FMT_E_DATA;
-  if (!rm) rmOrder = nullptr;
-  uint16_t* legacy = nullptr;
-  const bool adj = b->adjusts != nullptr;
-  if (adj) {
-    prepareNumbers(b);
-    g_legacyStride = fmt_mt::Doc<true, G, false, true>::kCapLeaves;
-    g_legacy.assign(static_cast<size_t>(b->n_docs) * g_legacyStride, 0xFFFFu);
-    legacy = g_legacy.data();
-  }
-  auto go = [&](auto obT, auto rmT, auto adjT) {
-    return replayAll<decltype(obT)::value, G, decltype(rmT)::value, decltype(adjT)::value>(
-        b, headers, leaves, chars, props, catchup, capCatchup, rmOrder, capRm, nullptr, false, 0, 0, nullptr, nullptr,
-        legacy, hugeCk);
-  };
-  using T = std::true_type;
-  using F = std::false_type;
-  if (adj) return rm ? go(T{}, T{}, T{}) : go(T{}, F{}, T{});
-  if (ob) return rm ? go(T{}, T{}, F{}) : go(T{}, F{}, F{});
-  return rm ? go(F{}, T{}, F{}) : go(F{}, F{}, F{});
+  MtRoute R;
+  if (const int rc = emu::planRouteOf(b, true, true, 0, -1, R)) return rc;
+  if (R.large.rm && rmOrder == nullptr) return FMT_E_DATA;
+  if (R.large.adj) prepareNumbers(b);
+  const Call c{b, headers, leaves, chars, props, catchup, capCatchup, R.large.rm ? rmOrder : nullptr, capRm, hugeCk};
+  return oneTier(c, MtTier::kLarge, R.large);
 }
 
 uint32_t emu_huge_ckpt_words() { return fmt_ckpt::kWords; }
 
-// f4 batches (local submissions, acks, rollbacks, reconnects), as the runtime runs them (round 6): the
-// small tier's Loc variant over every document, then the large tier's over the documents it could not
-// hold, from their first op (results at large strides). Mode 3: the compact tier's Loc variant first,
-// the small tier's over what it could not hold, then the large tier's (FMT_LOCAL_PATH 2). largeOnly: every
-// document in the large tier (round 5's path); 2: the compact tier alone (its statuses, diagnostics).
-// Annotate-adjust batches run the Adj local variants (Doc<false, C, false, true, true>), with the
-// batch's number tables (emu_mt_numbers) and legacy views (emu_mt_legacy_props).
+// f4 batches (local submissions, acks, rollbacks, reconnects): the local route and its large pass (results
+// at large strides). largeOnly 0: FMT_LOCAL_PATH 1 (small, then large from the first op); 3: FMT_LOCAL_PATH 2,
+// the compact tier first; 2: that route's first step alone (its statuses); 1: every document in the large tier.
+// Annotate-adjust batches: the Adj local variants, with emu_mt_numbers and emu_mt_legacy_props.
 int emu_mt_replay_local(const fmt_mt_batch* b, fmt_mt_doc_result* headers, fmt_mt_leaf* leaves, uint16_t* chars,
                         fmt_mt_propset* props, int largeOnly) {
   g_nums.clear();
   g_legacyStride = 0;
   prepareLocal(b->n_docs);
-  if (b->adjusts != nullptr) {
-    prepareNumbers(b);
-    return replayLocal<true>(b, headers, leaves, chars, props, largeOnly);
-  }
-  return replayLocal<false>(b, headers, leaves, chars, props, largeOnly);
+  if (b->adjusts != nullptr) prepareNumbers(b);
+  MtRoute R;
+  if (const int rc = emu::planRouteOf(b, true, true, 0, largeOnly >= 2 ? 2 : 1, R, MtVariant{false, false, false, true})) return rc;
+  const Call c{b, headers, leaves, chars, props};
+  if (largeOnly == 1) return oneTier(c, MtTier::kLarge, R.large);
+  if (largeOnly == 2) R.nSteps = 1;
+  return cascade(c, R, largeOnly != 2);
 }
 
 // Document d's regenerated ops (and their text) after the last emu_mt_replay_local: copies <= the

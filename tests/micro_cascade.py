@@ -23,8 +23,10 @@ def lib():
     if _lib is None:
         src = os.path.join(HERE, "emu", "mt_emu_tiers.cpp")
         csrc = os.path.join(HERE, "..", "fluidframework_amd", "csrc")
-        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + \
-               [os.path.join(csrc, f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h")]
+        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "emu", "emu_route.h"),
+                os.path.join(HERE, "..", "include", "fmt.h")] + \
+               [os.path.join(csrc, f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h", "mt_plan.h",
+                                                "mt_route.h", "mt_route_words.h")]
         if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
             _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], LIB_PATH, src)
@@ -35,6 +37,7 @@ def lib():
         L.emu_descend_consts.argtypes = [ctypes.POINTER(ctypes.c_int32)]
         L.emu_tier_launch.argtypes = ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 +
                                       [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4)
+        L.emu_mt_route.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_uint32]
         L.emu_bind_resumes.argtypes = [ctypes.c_int] * 6
         L.emu_bind_collect.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
         _lib = L
@@ -45,6 +48,19 @@ def caps(tier):
     a, b = ctypes.c_uint32(), ctypes.c_uint32()
     assert lib().emu_micro_caps(tier, ctypes.byref(a), ctypes.byref(b)) == 0
     return a.value, b.value
+
+
+def route(batch, ckpt_slab=True, desc_slab=True, rounds=0, local_path=-1):
+    """The route the runtime plans for `batch` (csrc/mt_route.h), read from the emulation library: a
+    native.MtRouteResult. rounds: other than the build's kDescendRounds."""
+    from fluidframework_amd.native import parse_mt_route
+
+    b, keep = batch_struct(batch)
+    w = np.zeros(1024, dtype=np.uint32)
+    n = lib().emu_mt_route(ctypes.addressof(b), int(ckpt_slab), int(desc_slab), rounds, local_path, _p(w), len(w))
+    del keep
+    assert n > 0, "the plan refuses the batch"
+    return parse_mt_route(w[:n])
 
 
 def ckpt_layout():

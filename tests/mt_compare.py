@@ -31,7 +31,7 @@ def emu_lib():
     global _emu
     if _emu is None:
         src = os.path.join(HERE, "emu", "mt_emu.cpp")
-        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h", "mt_plan.h")]
+        deps = [src, os.path.join(HERE, "emu", "emu_batch.h"), os.path.join(HERE, "emu", "emu_route.h"), os.path.join(HERE, "..", "include", "fmt.h")] + [os.path.join(HERE, "..", "fluidframework_amd", "csrc", f) for f in ("mt_bind.h", "mt_engine.h", "wave.h", "huge_ckpt.h", "adjust.h", "mt_plan.h", "mt_route.h")]
         if not os.path.exists(EMU_PATH) or os.path.getmtime(EMU_PATH) < max(os.path.getmtime(d) for d in deps):
             os.makedirs(os.path.dirname(EMU_PATH), exist_ok=True)
             _build_atomic(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"], EMU_PATH, src)
@@ -291,7 +291,8 @@ def _p(a):
 
 def emu_replay(batch, cap_catchup=0, force_ob=False, large=False, cap_rm=0):
     """Run the engine source under host emulation (small tier, or the large tier the runtime replays
-    overflowing documents in); returns (headers, leaves, chars, props), plus the catch-up ranges
+    overflowing documents in; large = 3 / 4: the batch's route as the runtime plans it, csrc/mt_route.h, so a
+    plain batch starts in the micro tier and runs the step-down rounds, not compact -> small only); returns (headers, leaves, chars, props), plus the catch-up ranges
     (n_docs, cap_catchup) when cap_catchup > 0, then the remove-order entries (n_docs, cap_rm) when
     cap_rm > 0."""
     cl, cc, cp = emu_caps(large)

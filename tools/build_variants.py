@@ -70,10 +70,6 @@ def build(name, edits, rev=None, flags=()):
     return out
 
 
-_LB = "return launchTier<false, S, false, kMtWaves, 2>(batch, out, docList, count, esc, numCUs, stream);"
-LB1 = ("mergetree.hip", _LB, _LB.replace("kMtWaves, 2>", "kMtWaves, 1>"))
-LB3 = ("mergetree.hip", _LB, _LB.replace("kMtWaves, 2>", "kMtWaves, 3>"))
-LB4 = ("mergetree.hip", _LB, _LB.replace("kMtWaves, 2>", "kMtWaves, 4>"))
 NODPP = ("wave.h", "#define FMT_USE_DPP 1", "#define FMT_USE_DPP 0")
 
 NOFENCE = ("wave.h", """FMT_DEV void waveSync() {
@@ -108,8 +104,8 @@ HW8 = [("huge_engine.h", "  static constexpr int kWaves = 4;", "  static constex
 
 # the small tier's obliterate variant (escalated obliterate documents) at 1 wave/SIMD: 512 registers a
 # wave, so its 32 spilled VGPRs go to AGPRs instead of scratch memory
-OB_S1 = ("mergetree.hip", "    return launchTier<true, S, false, kMtWaves, 2>(batch, out, esc2 + 1, count, esc, numCUs, stream, esc2, n1);",
-         "    return launchTier<true, S, false, kMtWaves, 1>(batch, out, esc2 + 1, count, esc, numCUs, stream, esc2, n1);")
+OB_S1 = ("mergetree.hip", "case mtKey(true, false): return launchTier<true, S, false, kMtWaves, 2>(a);",
+         "case mtKey(true, false): return launchTier<true, S, false, kMtWaves, 1>(a);")
 
 # op records and insert text through a wave-uniform base (SGPRs) plus a small lane offset, so the
 # loads take the saddr form and neither the loop index nor the arena pointers live in VGPRs (the
@@ -207,14 +203,11 @@ SHIFT4 = [("mt_engine.h", """    const int count = nChars - from;
 VISBF = [("mt_engine.h", '  FMT_DEV void visLengths(int refSeq, int client, Lane<VR>& vis, int nr) const {\n    FOR_ROWS(r, 0, nr) {\n      FOR_LANES(l) {\n        const uint32_t w0 = LANE(W[0])[r];\n        const int32_t ins = static_cast<int32_t>(LANE(W[1])[r]);\n        const int32_t rm = static_cast<int32_t>(LANE(W[2])[r]);\n        const int32_t ic = fClient(LANE(W[4])[r]);\n        const bool present = (ins <= refSeq || ic == client) && !(rm <= refSeq || removedBy(l, r, client));\n        LANE(vis)[r] = present ? fLen(w0) : 0u;\n      }\n    }\n  }', '  FMT_DEV void visLengths(int refSeq, int client, Lane<VR>& vis, int nr) const {\n    // branch-free: every term is a 0/1 word in a VGPR (shifts of differences, which cannot overflow:\n    // stamps are in [0, 2^31)), so no lane masks are combined in scalar registers\n    const bool hiW = C::kWords > 5 && client >= 32;\n    const uint32_t sh = client < 0 ? 0u : static_cast<uint32_t>(client & 31);\n    const uint32_t cm = client < 0 ? 0u : 1u;\n    const uint32_t cl8 = static_cast<uint32_t>(client) & 0xFFu;\n    FOR_ROWS(r, 0, nr) {\n      FOR_LANES(l) {\n        const uint32_t w0 = LANE(W[0])[r];\n        const uint32_t ins = LANE(W[1])[r];\n        const uint32_t rm = LANE(W[2])[r];\n        const uint32_t insLE = ((static_cast<uint32_t>(refSeq) - ins) >> 31) ^ 1u;\n        const uint32_t rmLE = ((static_cast<uint32_t>(refSeq) - rm) >> 31) ^ 1u;\n        const uint32_t icEq = (((LANE(W[4])[r] >> 24) ^ cl8) - 1u) >> 31;\n        const uint32_t rmb = ((hiW ? LANE(W[C::kWords > 5 ? 5 : 3])[r] : LANE(W[3])[r]) >> sh) & cm;\n        const uint32_t present = (insLE | icEq) & ((rmLE | rmb) ^ 1u);\n        LANE(vis)[r] = fLen(w0) * present;\n      }\n    }\n  }')]
 
 VARIANTS = {
-    # f4 local batches' compact tier at 2 waves/SIMD (256 VGPRs: no spills) instead of 3
-    "locCL": [("mergetree_local.hip", "#define FMT_LOCAL_PATH 2", "#define FMT_LOCAL_PATH 0")],
-    "locSL": [("mergetree_local.hip", "#define FMT_LOCAL_PATH 2", "#define FMT_LOCAL_PATH 1")],
     "locCSL": [],
     # the local small tier at 1 wave/SIMD (512 registers with AGPRs: no spills) instead of 2
     "locW1": [("mergetree_local.hip",
-               "return launchTier<false, S, false, kMtWavesLocal, 2, false, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);",
-               "return launchTier<false, S, false, kMtWavesLocal, 1, false, true>(batch, out, docList, count, esc, numCUs, stream, nullptr, n1);")],
+               "return launchTier<false, S, false, kMtWavesLocal, 2, false, true>(a);",
+               "return launchTier<false, S, false, kMtWavesLocal, 1, false, true>(a);")],
     "t3lat": [],  # (working tree: huge tier with its block count / flags loaded beside the leaf fields)
     # huge tier without its per-phase shader-clock reads (ProfScope's s_memtime pairs)
     "t3noclk": [("huge_engine.h", "    return __builtin_amdgcn_s_memtime();", "    return 0;")],
@@ -247,8 +240,7 @@ VARIANTS = {
                  "  FMT_DEV static uint32_t rd(const uint32_t* p) { return *p; }\n  FMT_DEV static int32_t rd(const int32_t* p) { return *p; }\n  FMT_DEV static uint32_t ldu(const uint32_t* p) { return uni(*p); }\n  FMT_DEV static int32_t ldi(const int32_t* p) { return uni(*p); }")],
     "heap2": [],  # (working tree: hole-moving heap sifts, both children read together)
     # obliterate cascade: the small tier at 1 wave/SIMD (512 registers a wave: the overflow in AGPRs)
-    "ob_o1": [("mergetree.hip", "  if (obliterate)\n    return launchTier<true, S, false, kMtWaves, 2>(batch, out, esc2 + 1,",
-               "  if (obliterate)\n    return launchTier<true, S, false, kMtWaves, 1>(batch, out, esc2 + 1,")],
+    "ob_o1": [OB_S1],
     "ob_base": [],
     "gq": [],  # (working tree: HugeState / HugeInputs buffers typed as global memory)
     "cur2": [],
@@ -269,12 +261,8 @@ VARIANTS = {
     "sw2": [("mergetree.hip", "constexpr int kMtWaves = 4;  // small tier: 4 documents per workgroup, 2 waves/SIMD",
              "constexpr int kMtWaves = 2;  // small tier: 4 documents per workgroup, 2 waves/SIMD")],
     "nofence": [NOFENCE],
-    "lb1": [LB1],
-    "lb3": [LB3],
-    "lb4": [LB4],
     "nodpp": [NODPP],
     "rows4": ROWS4,
-    "rows4_lb3": ROWS4 + [LB3],
     "map_nt": [MAP_NT],
     "map_w8": [MAP_W8],
     "map_w2": [MAP_W2],

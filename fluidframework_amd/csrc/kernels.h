@@ -10,6 +10,7 @@
 #include "mt_bind.h"
 #include "mt_route.h"
 #include "pos_plan.h"
+#include "range_plan.h"
 #include "runs_plan.h"
 #include "text_plan.h"
 
@@ -164,6 +165,16 @@ hipError_t launchPosTileUnits(const fmt_mt_doc_result* hdrs, const SumView* view
                               uint32_t nItems, fmt_plan::PosTileUnits* tileUnits, int numCUs, hipStream_t stream);
 hipError_t launchPosResolve(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::PosDevQuery* queries,
                             uint64_t nDev, uint64_t nQueries, fmt_mt_pos_hit* out, int numCUs, hipStream_t stream);
+
+// Bulk range reads (range.hip; include/fmt_range.h; views, items and offsets decided on the host: range_plan.h;
+// the sizing pass over (view, tile) items is launchPosTileUnits). One wave per item. launchRangeTileUnits writes
+// the text units of each item; launchRangeGather copies each item's units (a placeholder per Marker when
+// there is one) to out + itemBase[item], every index below cap.
+hipError_t launchRangeTileUnits(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::RangeItem* items,
+                                uint32_t nItems, unsigned long long* itemUnits, int numCUs, hipStream_t stream);
+hipError_t launchRangeGather(const fmt_mt_doc_result* hdrs, const SumView* views, const fmt_plan::RangeItem* items,
+                             uint32_t nItems, uint16_t placeholder, const unsigned long long* itemBase, uint16_t* out,
+                             uint64_t cap, int numCUs, hipStream_t stream);
 
 struct MtCaps {
   uint32_t leaves, chars, props;

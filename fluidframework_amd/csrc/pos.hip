@@ -25,6 +25,7 @@
 #include "../../include/fmt.h"
 #include "../../include/fmt_pos.h"
 #include "kernels.h"
+#include "pos_view.h"
 #include "sum_wave.h"
 
 namespace fmt_kernels {
@@ -34,18 +35,6 @@ namespace {
 using fmt_plan::PosDevQuery;
 using fmt_plan::PosItem;
 using fmt_plan::PosTileUnits;
-
-__device__ __forceinline__ uint32_t posUnitsOf(const fmt_mt_leaf& L) { return (L.pad & FMT_MT_LEAF_MARKER) != 0 ? 1u : L.len; }
-
-__device__ __forceinline__ bool posVisibleLocal(const fmt_mt_leaf& L) { return L.rm_seq == FMT_NOT_REMOVED; }
-
-__device__ __forceinline__ bool posVisible(const fmt_mt_leaf& L, int32_t refSeq, int32_t client) {
-  if (refSeq == FMT_MT_VIEW_LOCAL) return posVisibleLocal(L);
-  const uint32_t c = static_cast<uint32_t>(client) & 63u;
-  const bool inserted = L.ins_seq <= refSeq || static_cast<int32_t>(L.ins_client) == client;
-  const bool removed = L.rm_seq <= refSeq || ((L.rm_clients >> c) & 1ull) != 0;
-  return inserted && !removed;
-}
 
 }  // namespace
 

@@ -18,6 +18,7 @@
 #include "../../include/fmt_map_summary.h"
 #include "../../include/fmt_map_tiered.h"
 #include "../../include/fmt_pos.h"
+#include "../../include/fmt_range.h"
 #include "../../include/fmt_runs.h"
 #include "../../include/fmt_text.h"
 #include "../../include/fmt_v1.h"
@@ -323,6 +324,17 @@ struct fmt_ctx {
   DevBuf<fmt_plan::PosDevQuery> posQueries;
   DevBuf<fmt_mt_pos_hit> posHits;
   PinnedBuf<fmt_plan::PosTileUnits> posHostUnits;
+  // bulk range reads (fmt_mt_fetch_text_ranges, range.hip): the plan of the call over the frame's tiles
+  // (range_plan.h), the (view, tile) sizing items and their units, the range items with their text units and
+  // bases, the packed text. Its own buffers and nothing cached between calls: no other read sees them.
+  fmt_plan::RangePlan rngPlan;
+  DevBuf<fmt_plan::PosItem> rngViewItems;
+  DevBuf<fmt_plan::PosTileUnits> rngViewUnits;
+  PinnedBuf<fmt_plan::PosTileUnits> rngHostViewUnits;
+  DevBuf<fmt_plan::RangeItem> rngItems;
+  DevBuf<unsigned long long> rngUnits, rngBases;
+  PinnedBuf<uint64_t> rngHostUnits;
+  DevBuf<uint16_t> rngPacked;
 };
 
 namespace {
@@ -2674,6 +2686,64 @@ int fmt_mt_query_positions(fmt_ctx* c, const uint64_t* qOffsets, const fmt_mt_po
   return FMT_OK;
 }
 
+int fmt_mt_fetch_text_ranges(fmt_ctx* c, uint16_t placeholder, const uint64_t* qOffsets, const fmt_mt_range_query* q,
+                             uint64_t nQueries, fmt_mt_range_hit* hits, uint64_t* total, uint16_t* out, uint64_t cap) {
+  if (const int rc = mtReadEntry(c, qOffsets != nullptr && total != nullptr && !(nQueries && (q == nullptr || hits == nullptr)),
+                                 "fmt_mt_fetch_text_ranges", "fmt_mt_fetch_text_ranges: bad arguments"))
+    return rc;
+  const uint32_t nd = c->mtDocs;
+  if (!fmt_plan::posOffsetsValid(qOffsets, nd, nQueries))
+    return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_text_ranges: q_offsets must ascend from 0 to n_queries");
+  *total = 0;
+  if (nQueries == 0) return FMT_OK;
+  // the statuses the headers decide, the views and their (view, tile) items over the frame's tiles
+  const fmt_ctx::ReadFrame* F = nullptr;
+  if (const int frc = frameTiles(c, "fmt_mt_fetch_text_ranges: more than 2^32 - 1 views or work items", &F)) return frc;
+  fmt_plan::RangePlan& P = c->rngPlan;
+  int rc = fmt_plan::planRangeViews(F->hdr.data(), nd, c->mtPlan.obliterates, F->tiles, qOffsets, q, nQueries, hits, P);
+  if (rc != FMT_OK) return setErr(c, rc, "fmt_mt_fetch_text_ranges: more than 2^32 - 1 views or work items");
+  // pass A (pos.hip): every (view, tile) item's units in its view; the prefixes and the cut into items on the host
+  const size_t nv = P.views.items.size();
+  FMT_HIP(c, c->rngHostViewUnits.reserve(nv));
+  if (nv) {
+    FMT_HIP(c, c->rngViewItems.reserve(nv));
+    FMT_HIP(c, c->rngViewUnits.reserve(nv));
+    FMT_HIP(c, hipMemcpyAsync(c->rngViewItems.p, P.views.items.data(), nv * sizeof(fmt_plan::PosItem), hipMemcpyHostToDevice, c->stream));
+    FMT_HIP(c, fmt_kernels::launchPosTileUnits(c->mtHdr.p, c->sumViews.p, c->rngViewItems.p, static_cast<uint32_t>(nv),
+                                               c->rngViewUnits.p, c->numCUs, c->stream));
+    FMT_HIP(c, hipMemcpyAsync(c->rngHostViewUnits.p, c->rngViewUnits.p, nv * sizeof(fmt_plan::PosTileUnits), hipMemcpyDeviceToHost,
+                              c->stream));
+    FMT_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  rc = fmt_plan::cutRanges(P, F->tiles, c->rngHostViewUnits.p, q, nQueries, hits);
+  if (rc != FMT_OK) return setErr(c, rc, "fmt_mt_fetch_text_ranges: more than 2^32 - 1 work items");
+  // pass B: the text units of every item (with a placeholder they are its positions); the offsets on the host
+  const size_t ni = P.items.size();
+  if (ni) {
+    FMT_HIP(c, c->rngItems.reserve(ni));
+    FMT_HIP(c, stagedCopy(c, c->rngItems.p, P.items.data(), ni * sizeof(fmt_plan::RangeItem), true));
+  }
+  if (ni && placeholder == 0) {
+    FMT_HIP(c, c->rngUnits.reserve(ni));
+    FMT_HIP(c, c->rngHostUnits.reserve(ni));
+    FMT_HIP(c, fmt_kernels::launchRangeTileUnits(c->mtHdr.p, c->sumViews.p, c->rngItems.p, static_cast<uint32_t>(ni), c->rngUnits.p,
+                                                 c->numCUs, c->stream));
+    FMT_HIP(c, stagedCopy(c, c->rngHostUnits.p, c->rngUnits.p, ni * sizeof(uint64_t), false));
+  }
+  *total = fmt_plan::rangeOffsets(P, ni && placeholder == 0 ? c->rngHostUnits.p : nullptr, nQueries, hits);
+  if (out == nullptr) return FMT_OK;
+  if (cap < *total) return setErr(c, FMT_E_USAGE, "fmt_mt_fetch_text_ranges: cap below the units of the ranges");
+  if (*total == 0) return FMT_OK;
+  // pass C: every item's units to its base in the packed text, then one staged copy of exactly those
+  FMT_HIP(c, c->rngBases.reserve(ni));
+  FMT_HIP(c, c->rngPacked.reserve(*total));
+  FMT_HIP(c, stagedCopy(c, c->rngBases.p, P.itemBase.data(), ni * sizeof(uint64_t), true));
+  FMT_HIP(c, fmt_kernels::launchRangeGather(c->mtHdr.p, c->sumViews.p, c->rngItems.p, static_cast<uint32_t>(ni), placeholder,
+                                            c->rngBases.p, c->rngPacked.p, *total, c->numCUs, c->stream));
+  FMT_HIP(c, stagedCopy(c, out, c->rngPacked.p, *total * sizeof(uint16_t), false));
+  return FMT_OK;
+}
+
 int fmt_mt_fetch_remove_order(fmt_ctx* c, uint32_t doc, fmt_mt_remove_order* out, uint32_t cap) {
   if (const int rc = mtReadEntry(c, c && doc < c->mtDocs && !(out == nullptr && cap > 0), "fmt_mt_fetch_remove_order",
                                  "fmt_mt_fetch_remove_order: bad arguments"))
@@ -2930,6 +3000,56 @@ int fmt_internal_pos_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_
     for (const fmt_plan::PosDevQuery& d : P.dev)
       w.insert(w.end(), {uint64_t{d.doc}, uint64_t{d.firstLeaf}, uint64_t{d.nLeaves}, uint64_t{d.pos}, sx(d.refSeq), sx(d.client),
                          uint64_t{d.viewBase}, uint64_t{d.localBase}, d.out});
+  }
+  *out = w.data();
+  *nWords = w.size();
+  return FMT_OK;
+}
+
+// Test hook (not part of fmt_range.h): fmt_mt_fetch_text_ranges' host half (range_plan.h) over host headers, no
+// device needed. tile_leaves 0: the kernels' tile. hits[n_queries] receives the records as the host leaves
+// them. Words: the number of views; the views (doc, ref_seq, client, first item; signed values
+// sign-extended); the number of (view, tile) items; those items (doc, first leaf, leaves, view); when
+// tile_units (two per such item: view, local; so from a second call) is given, the number of range items
+// and the items (doc, first leaf, leaves, lo, hi, ref_seq, client, query); and, when placeholder != 0 or
+// item_units (one per range item, so from a third call) is given, every item's base and *total. Returns the
+// plan's status. Valid until the calling thread's next call.
+int fmt_internal_range_plan(const fmt_mt_doc_result* hdrs, uint32_t nDocs, uint32_t obliterates, uint32_t tileLeaves,
+                            uint32_t placeholder, const uint64_t* qOffsets, const fmt_mt_range_query* q, uint64_t nQueries,
+                            const uint64_t* tileUnits, uint64_t nTileUnits, const uint64_t* itemUnits, uint64_t nItemUnits,
+                            fmt_mt_range_hit* hits, uint64_t* total, const uint64_t** out, uint64_t* nWords) {
+  static thread_local std::vector<uint64_t> w;
+  if ((nDocs && hdrs == nullptr) || qOffsets == nullptr || (nQueries && (q == nullptr || hits == nullptr)) || total == nullptr ||
+      out == nullptr || nWords == nullptr)
+    return FMT_E_USAGE;
+  fmt_plan::TextPlan T;
+  fmt_plan::planTextTiles(hdrs, nDocs, tileLeaves, T);
+  fmt_plan::RangePlan P;
+  int rc = fmt_plan::planRangeViews(hdrs, nDocs, obliterates != 0, T, qOffsets, q, nQueries, hits, P);
+  if (rc != FMT_OK) return rc;
+  *total = 0;
+  auto sx = [](int32_t x) { return static_cast<uint64_t>(static_cast<int64_t>(x)); };
+  w.assign(1, P.views.views.size());
+  for (const fmt_plan::PosView& v : P.views.views) w.insert(w.end(), {uint64_t{v.doc}, sx(v.refSeq), sx(v.client), v.firstItem});
+  w.push_back(P.views.items.size());
+  for (const fmt_plan::PosItem& it : P.views.items) w.insert(w.end(), {it.doc, it.firstLeaf, it.nLeaves, it.view});
+  if (tileUnits != nullptr) {
+    if (nTileUnits != P.views.items.size()) return FMT_E_USAGE;
+    std::vector<fmt_plan::PosTileUnits> u(P.views.items.size() + 1);
+    std::memcpy(u.data(), tileUnits, P.views.items.size() * sizeof(fmt_plan::PosTileUnits));
+    rc = fmt_plan::cutRanges(P, T, u.data(), q, nQueries, hits);
+    if (rc != FMT_OK) return rc;
+    w.push_back(P.items.size());
+    for (size_t k = 0; k < P.items.size(); k++) {
+      const fmt_plan::RangeItem& it = P.items[k];
+      w.insert(w.end(), {uint64_t{it.doc}, uint64_t{it.firstLeaf}, uint64_t{it.nLeaves}, uint64_t{it.lo}, uint64_t{it.hi}, sx(it.refSeq),
+                         sx(it.client), P.itemQuery[k]});
+    }
+    if (placeholder != 0 || itemUnits != nullptr) {
+      if (placeholder == 0 && nItemUnits != P.items.size()) return FMT_E_USAGE;
+      *total = fmt_plan::rangeOffsets(P, placeholder == 0 ? itemUnits : nullptr, nQueries, hits);
+      w.insert(w.end(), P.itemBase.begin(), P.itemBase.end());
+    }
   }
   *out = w.data();
   *nWords = w.size();

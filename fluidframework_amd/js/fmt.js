@@ -54,6 +54,7 @@ const MT_OP_BYTES = 32, MAP_OP_BYTES = 16, LEAF_BYTES = 32, DOC_RESULT_BYTES = 4
 const CATCHUP_BYTES = 16, SNAPSHOT_DOC_BYTES = 32;
 const NO_PROPS = 0xffffffff;
 const PROPS_MAX = 8, FMT_MT_PROPS_CONT = 0xffffffff; // fmt.h: entries per prop-set record; n of a continuation record
+const RANGE_TO_END = 0xffffffff; // fmt_range.h FMT_MT_RANGE_TO_END: a range query's end naming the view's length
 const POS_VIEW_LOCAL = 0x7fffffff; // fmt_pos.h FMT_MT_VIEW_LOCAL: a position query's refSeq naming the local view
 
 let addon = null;
@@ -1438,6 +1439,48 @@ class MergeTreeReplay {
 		});
 		return out;
 	}
+	/**
+	 * The text of many ranges in one device pass (fmt_mt_fetch_text_ranges, fmt_range.h): the reference's
+	 * getText(start, end) / getTextWithPlaceholders(start, end) in bulk, in any view. queries: an array of
+	 * {doc, start, end, refSeq, client} in any order; end absent (or RANGE_TO_END): the view's length; refSeq
+	 * absent (or POS_VIEW_LOCAL): the local view, else the view of short client id `client` at refSeq.
+	 * placeholder: 0 (default) drops Markers, else that UTF-16 unit stands for each. Returns one object per
+	 * query, in the queries' order: {status, span, text}; text is null for a query that cannot be answered,
+	 * which carries its own status (fmt_range.h); the call throws only for misuse.
+	 */
+	textRanges(queries, placeholder = 0) {
+		const n = this.batch.nDocs;
+		const order = queries.map((_, i) => i);
+		for (const q of queries) {
+			if (!Number.isInteger(q.doc) || q.doc < 0 || q.doc >= n) throw new RangeError(`textRanges: document ${q.doc} outside the batch`);
+		}
+		order.sort((a, b) => queries[a].doc - queries[b].doc || a - b);
+		const offs = new BigUint64Array(n + 1);
+		const qv = new DataView(new ArrayBuffer(16 * queries.length));
+		order.forEach((i, k) => {
+			const q = queries[i];
+			offs[q.doc + 1]++;
+			qv.setUint32(16 * k, q.start, true);
+			qv.setUint32(16 * k + 4, q.end === undefined || q.end === null ? RANGE_TO_END : q.end, true);
+			qv.setInt32(16 * k + 8, q.refSeq === undefined || q.refSeq === null ? POS_VIEW_LOCAL : q.refSeq, true);
+			qv.setInt32(16 * k + 12, q.client || 0, true);
+		});
+		for (let d = 0; d < n; d++) offs[d + 1] += offs[d];
+		const r = native().fetchTextRanges(this.engine.ctx, n, placeholder, offs.buffer, qv.buffer);
+		const hv = new DataView(r.hits);
+		const out = new Array(queries.length);
+		order.forEach((i, k) => {
+			const o = 24 * k, status = hv.getInt32(o + 16, true);
+			const at = Number(hv.getBigUint64(o, true)), units = hv.getUint32(o + 8, true);
+			let text = null;
+			if (status === 0) {
+				text = "";
+				for (let a = at; a < at + units; a += 8192) text += String.fromCharCode.apply(null, r.units.subarray(a, Math.min(a + 8192, at + units)));
+			}
+			out[i] = { status, span: hv.getUint32(o + 12, true), text };
+		});
+		return out;
+	}
 	getLength(doc) {
 		return this.header(doc).visibleLength;
 	}
@@ -1611,5 +1654,5 @@ module.exports = {
 	summary,
 	constants: { MT_INSERT, MT_REMOVE, MT_ANNOTATE, MT_GROUP, MAP_SET, MAP_DELETE, MAP_CLEAR,
 		MAP_VALUE_UNDEFINED, MAP_ABSENT, FMT_MT_F_GROUP_CONT, FMT_MT_F_CATCHUP, NOT_REMOVED,
-		FMT_MT_F_LOCAL, FMT_MT_F_ACK, FMT_MT_F_ROLLBACK, FMT_MT_F_REGEN, FMT_MT_LOCAL_SEQ_BASE: 0x40000000, POS_VIEW_LOCAL },
+		FMT_MT_F_LOCAL, FMT_MT_F_ACK, FMT_MT_F_ROLLBACK, FMT_MT_F_REGEN, FMT_MT_LOCAL_SEQ_BASE: 0x40000000, POS_VIEW_LOCAL, RANGE_TO_END },
 };

@@ -28,6 +28,7 @@
 //   fetchTextAll(ctx, nDocs, placeholder) -> {offsets, text}         fmt_mt_fetch_text_all (fmt_text.h)
 //   fetchPropRunsAll(ctx, nDocs) -> {runOffsets, runs, propOffsets, props}  fmt_mt_fetch_prop_runs_all + fmt_mt_fetch_props_all (fmt_runs.h)
 //   queryPositions(ctx, nDocs, qOffsets, queries) -> hits              fmt_mt_query_positions (fmt_pos.h)
+//   fetchTextRanges(ctx, nDocs, placeholder, qOffsets, queries) -> {hits, units}   fmt_mt_fetch_text_ranges (fmt_range.h)
 //   fetchRegen(ctx, doc) -> {ops: ArrayBuffer, text: Uint16Array}     fmt_mt_fetch_regen (f4 reconnects)
 //   replayMap(ctx, batch) -> Promise<ArrayBuffer slots>              fmt_map_load + run + fetch
 //   replayMapSparse(ctx, batch, tiered?) -> Promise<{counts, entries}>  fmt_map_load_sparse + run + fetch
@@ -56,6 +57,7 @@
 #include "fmt_map_summary.h"
 #include "fmt_map_tiered.h"
 #include "fmt_pos.h"
+#include "fmt_range.h"
 #include "fmt_runs.h"
 #include "fmt_text.h"
 
@@ -1340,6 +1342,66 @@ napi_value QueryPositions(napi_env env, napi_callback_info info) {
   return hb;
 }
 
+// fetchTextRanges(ctx, nDocs, placeholder, qOffsets, queries) -> {hits: ArrayBuffer of 24-byte fmt_mt_range_hit
+// records, one per query; units: Uint16Array, the text of the ranges packed in query order}
+// (fmt_mt_fetch_text_ranges, fmt_range.h: the sizing call, then the fill). qOffsets: ArrayBuffer of nDocs + 1
+// uint64, ascending from 0 to the number of queries; queries: ArrayBuffer of 16-byte fmt_mt_range_query records
+// packed per document (nDocs = the loaded batch's document count).
+napi_value FetchTextRanges(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Ctx* c;
+  uint32_t nd, placeholder;
+  if (argc < 5 || !get_ctx(env, argv[0], &c) || !get_u32(env, argv[1], "nDocs", &nd) || !get_u32(env, argv[2], "placeholder", &placeholder))
+    return nullptr;
+  if (c->busy) {
+    throw_fmt(env, FMT_E_USAGE, "fetchTextRanges: a replay is running on this context");
+    return nullptr;
+  }
+  void *po = nullptr, *pq = nullptr;
+  size_t no = 0, nq = 0;
+  if (napi_get_arraybuffer_info(env, argv[3], &po, &no) != napi_ok || napi_get_arraybuffer_info(env, argv[4], &pq, &nq) != napi_ok) {
+    throw_fmt(env, FMT_E_USAGE, "fetchTextRanges: qOffsets and queries are ArrayBuffers");
+    return nullptr;
+  }
+  if (placeholder > 0xFFFFu || no != (size_t(nd) + 1) * sizeof(uint64_t) || nq % sizeof(fmt_mt_range_query) != 0) {
+    throw_fmt(env, FMT_E_USAGE, "fetchTextRanges: placeholder is a UTF-16 unit, qOffsets holds nDocs + 1 uint64, queries 16-byte records");
+    return nullptr;
+  }
+  using Fn = int (*)(fmt_ctx*, uint16_t, const uint64_t*, const fmt_mt_range_query*, uint64_t, fmt_mt_range_hit*, uint64_t*, uint16_t*,
+                     uint64_t);
+  const Fn fetch = reinterpret_cast<Fn>(libfmt_symbol("fmt_mt_fetch_text_ranges"));
+  if (fetch == nullptr) {
+    throw_fmt(env, FMT_E_UNSUPPORTED, "fetchTextRanges: the loaded libfmt has no fmt_mt_fetch_text_ranges");
+    return nullptr;
+  }
+  const uint64_t n = nq / sizeof(fmt_mt_range_query);
+  void *ph = nullptr, *pu = nullptr;
+  napi_value hb = nullptr, ub = nullptr, arr = nullptr, out = nullptr;
+  CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(n) * sizeof(fmt_mt_range_hit), &ph, &hb));
+  uint64_t total = 0;
+  int rc = fetch(c->ctx, uint16_t(placeholder), static_cast<const uint64_t*>(po), static_cast<const fmt_mt_range_query*>(pq), n,
+                 static_cast<fmt_mt_range_hit*>(ph), &total, nullptr, 0);
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  CHECK_NAPI(env, napi_create_arraybuffer(env, size_t(total) * sizeof(uint16_t), &pu, &ub));
+  if (total)
+    rc = fetch(c->ctx, uint16_t(placeholder), static_cast<const uint64_t*>(po), static_cast<const fmt_mt_range_query*>(pq), n,
+               static_cast<fmt_mt_range_hit*>(ph), &total, static_cast<uint16_t*>(pu), total);
+  if (rc != FMT_OK) {
+    throw_fmt(env, rc, fmt_last_error(c->ctx));
+    return nullptr;
+  }
+  CHECK_NAPI(env, napi_create_typedarray(env, napi_uint16_array, size_t(total), ub, 0, &arr));
+  CHECK_NAPI(env, napi_create_object(env, &out));
+  CHECK_NAPI(env, napi_set_named_property(env, out, "hits", hb));
+  CHECK_NAPI(env, napi_set_named_property(env, out, "units", arr));
+  return out;
+}
+
 napi_value FetchRegen(napi_env env, napi_callback_info info) {
   size_t argc = 2;
   napi_value argv[2];
@@ -1434,6 +1496,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fetchPropRunsAll", nullptr, FetchPropRunsAll, nullptr, nullptr, nullptr, napi_default, nullptr},
       // fmt_pos.h's bulk position queries, the same way
       {"queryPositions", nullptr, QueryPositions, nullptr, nullptr, nullptr, napi_default, nullptr},
+      // fmt_range.h's bulk range reads, the same way
+      {"fetchTextRanges", nullptr, FetchTextRanges, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof fns / sizeof fns[0], fns);
   napi_value sizes, v;

@@ -73,6 +73,11 @@ POS_HIT_DTYPE = np.dtype([("leaf", "<u4"), ("offset", "<u4"), ("leaf_start", "<u
 assert POS_QUERY_DTYPE.itemsize == 16 and POS_HIT_DTYPE.itemsize == 32
 VIEW_LOCAL = 0x7FFFFFFF  # fmt_pos.h FMT_MT_VIEW_LOCAL
 POS_F_MARKER, POS_F_END, POS_F_HIDDEN_LOCALLY = 1, 2, 4  # fmt_pos.h FMT_MT_POS_F_*
+# include/fmt_range.h (bulk range reads)
+RANGE_QUERY_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("ref_seq", "<i4"), ("client", "<i4")])
+RANGE_HIT_DTYPE = np.dtype([("text_off", "<u8"), ("units", "<u4"), ("span", "<u4"), ("status", "<i4"), ("pad", "<u4")])
+assert RANGE_QUERY_DTYPE.itemsize == 16 and RANGE_HIT_DTYPE.itemsize == 24
+RANGE_TO_END = 0xFFFFFFFF  # fmt_range.h FMT_MT_RANGE_TO_END
 
 from .streams import (NO_MARKER, RELPOS_DTYPE, SNAPSHOT_DOC_DTYPE, SNAPSHOT_INFO_DTYPE, SNAPSHOT_SEG_DTYPE,  # noqa: E402
                       STAMP_DTYPE)  # (include/fmt.h layouts)
@@ -291,6 +296,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
                            ("fmt_mt_query_positions", [P, P, P, U64, P]),
                            ("fmt_internal_pos_plan", [P, U32, U32, U32, P, P, U64, P, U64, P, ctypes.POINTER(P),
                                                       ctypes.POINTER(U64)]),
+                           ("fmt_mt_fetch_text_ranges", [P, ctypes.c_uint16, P, P, U64, P, P, P, U64]),
+                           ("fmt_internal_range_plan", [P, U32, U32, U32, U32, P, P, U64, P, U64, P, U64, P, ctypes.POINTER(U64),
+                                                        ctypes.POINTER(P), ctypes.POINTER(U64)]),
                            ("fmt_internal_map_summary_arrays", [P, P, P, P, U64]),
                            ("fmt_internal_map_summary_host_only", [P, ctypes.c_int])):
             if path == LIB_PATH or hasattr(L, name):  # (older experimental builds may lack them)
@@ -325,6 +333,8 @@ EXPORTED_SYMBOLS_TEXT = ["fmt_mt_fetch_text_all", "fmt_mt_text_tile_leaves"]
 EXPORTED_SYMBOLS_RUNS = ["fmt_mt_fetch_prop_runs_all", "fmt_mt_fetch_props_all"]
 # include/fmt_pos.h (bulk position queries)
 EXPORTED_SYMBOLS_POS = ["fmt_mt_query_positions"]
+# include/fmt_range.h (bulk range reads)
+EXPORTED_SYMBOLS_RANGE = ["fmt_mt_fetch_text_ranges"]
 MAP_SUMMARY_CONTENT = 0xFFFFFFFF    # tag of an ordered entry that stays in the header's "content"
 MAP_SUMMARY_DEVICE_MAX = 2048       # live entries per document the device tier orders (csrc/map_sum_plan.h)
 
@@ -667,6 +677,62 @@ def pos_plan(headers, queries, q_offsets, tile_units=None, obliterates: bool = F
         ndev = int(w[at])
         r.dev = w[at + 1 : at + 1 + 9 * ndev].reshape(ndev, 9)
         at += 1 + 9 * ndev
+    assert at == len(w)
+    return r
+
+
+class RangePlanResult:
+    """What range_plan read back (csrc/range_plan.h): `hits` (RANGE_HIT_DTYPE, one per query, as the host
+    leaves them), `views` ((n, 4) int64: doc, ref_seq, client, first item), `view_items` ((n, 4): doc, first
+    leaf, leaves, view: the sizing pass's work items); when tile units were given, `items` ((n, 8) int64: doc,
+    first leaf, leaves, lo, hi, ref_seq, client, query); and, when item units were given or there is a
+    placeholder, `item_base` (each item's first unit in the packed text) and `total`."""
+
+
+def range_plan(headers, queries, q_offsets, tile_units=None, item_units=None, placeholder: int = 0, obliterates: bool = False,
+               tile_leaves: int = 0) -> RangePlanResult:
+    """fmt_internal_range_plan: fmt_mt_fetch_text_ranges' host half over result headers (DOC_RESULT_DTYPE), no
+    device needed. tile_leaves 0: the kernels' tile. tile_units ((n_view_items, 2): units in the view, units
+    in the local view): also the cut of every range into items. item_units (one per item: its text units;
+    not needed with a placeholder): also the offsets. Raises EngineError(FMT_E_USAGE) for malformed
+    q_offsets."""
+    hdr = np.ascontiguousarray(headers, dtype=DOC_RESULT_DTYPE)
+    q = np.ascontiguousarray(queries, dtype=RANGE_QUERY_DTYPE)
+    offs = np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    if len(offs) != len(hdr) + 1:
+        raise EngineError(FMT_E_USAGE, f"{len(offs)} q_offsets for {len(hdr)} documents")
+    units = None if tile_units is None else np.ascontiguousarray(tile_units, dtype=np.uint64).reshape(-1, 2)
+    iunits = None if item_units is None else np.ascontiguousarray(item_units, dtype=np.uint64).reshape(-1)
+    hits = np.zeros(max(len(q), 1), dtype=RANGE_HIT_DTYPE)
+    P = ctypes.c_void_p
+    out, n, total = P(), ctypes.c_uint64(), ctypes.c_uint64()
+    rc = lib().fmt_internal_range_plan(_ptr(hdr) if len(hdr) else None, len(hdr), 1 if obliterates else 0, tile_leaves, placeholder,
+                                       _ptr(offs), _ptr(q) if len(q) else None, len(q),
+                                       None if units is None else _ptr(units if len(units) else np.zeros(2, np.uint64)),
+                                       0 if units is None else len(units),
+                                       None if iunits is None else _ptr(iunits if len(iunits) else np.zeros(1, np.uint64)),
+                                       0 if iunits is None else len(iunits), _ptr(hits), ctypes.byref(total), ctypes.byref(out),
+                                       ctypes.byref(n))
+    if rc != FMT_OK:
+        raise EngineError(rc, "fmt_internal_range_plan")
+    w = np.ctypeslib.as_array(ctypes.cast(out, ctypes.POINTER(ctypes.c_uint64)), (n.value,)).copy().view(np.int64)
+    r = RangePlanResult()
+    r.hits = hits[: len(q)]
+    nv = int(w[0])
+    r.views = w[1 : 1 + 4 * nv].reshape(nv, 4)
+    at = 1 + 4 * nv
+    ni = int(w[at])
+    r.view_items = w[at + 1 : at + 1 + 4 * ni].reshape(ni, 4)
+    at += 1 + 4 * ni
+    r.items = r.item_base = r.total = None
+    if units is not None:
+        nr = int(w[at])
+        r.items = w[at + 1 : at + 1 + 8 * nr].reshape(nr, 8)
+        at += 1 + 8 * nr
+        if placeholder != 0 or iunits is not None:
+            r.item_base = w[at : at + nr]
+            at += nr
+            r.total = int(total.value)
     assert at == len(w)
     return r
 
@@ -1042,6 +1108,33 @@ class Engine:
         out = np.zeros(max(len(q), 1), dtype=POS_HIT_DTYPE)
         self._check(self.L.fmt_mt_query_positions(self.h, _ptr(offs), _ptr(q) if len(q) else None, len(q), _ptr(out)))
         return out[: len(q)]
+
+    # ---- bulk range reads of the last merge-tree run (include/fmt_range.h)
+    def mt_text_ranges(self, queries, q_offsets, placeholder: int = 0):
+        """fmt_mt_fetch_text_ranges: the text of every range of every document in one device pass. queries:
+        RANGE_QUERY_DTYPE (start, end, ref_seq, client; end RANGE_TO_END: the view's length; ref_seq
+        VIEW_LOCAL: the local view), packed per document; q_offsets: n_docs + 1 offsets, ascending from 0 to
+        len(queries). placeholder as in mt_texts. Returns (hits RANGE_HIT_DTYPE[len(queries)], units
+        uint16[total]): range i's units at units[text_off : text_off + units] of hit i; a range that could
+        not be read carries its own status, the call raises only for misuse."""
+        q = np.ascontiguousarray(queries, dtype=RANGE_QUERY_DTYPE)
+        offs = np.ascontiguousarray(q_offsets, dtype=np.uint64)
+        if len(offs) != self._mt_docs + 1:
+            raise EngineError(FMT_E_USAGE, f"mt_text_ranges: {len(offs)} q_offsets for {self._mt_docs} documents")
+        hits = np.zeros(max(len(q), 1), dtype=RANGE_HIT_DTYPE)
+        total = ctypes.c_uint64()
+        args = (self.h, placeholder, _ptr(offs), _ptr(q) if len(q) else None, len(q), _ptr(hits), ctypes.byref(total))
+        self._check(self.L.fmt_mt_fetch_text_ranges(*args, None, 0))
+        units = np.zeros(max(int(total.value), 1), dtype="<u2")
+        self._check(self.L.fmt_mt_fetch_text_ranges(*args, _ptr(units), int(total.value)))
+        return hits[: len(q)], units[: int(total.value)]
+
+    def mt_range_strings(self, queries, q_offsets, placeholder: int = 0) -> list:
+        """mt_text_ranges as one str per query (lone surrogates kept), None for a query that failed."""
+        hits, units = self.mt_text_ranges(queries, q_offsets, placeholder)
+        raw = units.tobytes()
+        return [raw[2 * int(h["text_off"]) : 2 * (int(h["text_off"]) + int(h["units"]))].decode("utf-16-le", "surrogatepass")
+                if int(h["status"]) == FMT_OK else None for h in hits]
 
     def mt_positions_local(self, doc_ids, positions) -> np.ndarray:
         """mt_positions for local-view queries given as parallel arrays in any order: hit i answers

@@ -281,6 +281,16 @@ struct DocOutputs {
 #ifndef FMT_SCALAR_OPS
 #define FMT_SCALAR_OPS 0
 #endif
+// Diagnostic build of the host emulation only (-DFMT_SCOUR_COUNT, tools/scour_counts.py): every leaf-block
+// scour takes the serial pass and reports what its ballots predicted beside what the pass found.
+#if !FMT_GPU && defined(FMT_SCOUR_COUNT)
+extern "C" void fmtScourNote(int sibling, int pairs, int drops, uint32_t mergeMask, uint32_t dropMask);
+#define FMT_SCOUR_SLOW 1
+#define FMT_SCOUR_NOTE(sibling, pairs, drops, mergeMask, dropMask) fmtScourNote(sibling, pairs, drops, mergeMask, dropMask)
+#else
+#define FMT_SCOUR_SLOW 0
+#define FMT_SCOUR_NOTE(sibling, pairs, drops, mergeMask, dropMask) ((void)0)
+#endif
 enum ProfCat {
   kPfOpLoad, kPfScan, kPfSplit, kPfInsert, kPfRange, kPfLru, kPfZamboniOp, kPfWindow, kPfOutput,
   kPfInsChars, kPfInsShift, kPfZFind, kPfZChars, kPfZSerial, kPfZDelete, kPfZPack, kPfCount
@@ -3405,109 +3415,172 @@ class Doc {
   // ------------------------------------------------------------------ zamboni (zamboni.ts)
   // scourNode over leaf block b: drops tombstones removed at/below minSeq and appends acked,
   // same-props, appendable leaves onto the previous kept leaf. Returns the new child count.
-  FMT_DEV int scourLeafBlock(int b) {
+  //
+  // Two ballots over the block's one or two rows decide first whether the serial pass is needed:
+  //   drop: removed at/below minSeq (unlinked whatever its neighbours are);
+  //   E:    can take part in an append at all, as head or as appended leaf: not held (Loc), not
+  //         removed, inserted at/below minSeq, not a marker, length > 0.
+  // In the serial pass leaf k is appended only while `prev` is set, and `prev` survives leaf k - 1 only
+  // if that leaf was appended or became a head with length > 0 that is no marker; either way both are in
+  // E. So with no two neighbouring leaves in E nothing is appended: without drops the block stays as it
+  // is (kept = cnt; nothing is read from the text, nothing written to s->tmp), and with drops the masks
+  // are the drop ballot itself and only the dropped leaves' text spans are looked up.
+  static constexpr bool kScourDropOnly = true;
+  FMT_DEV int scourLeafBlock(int b, [[maybe_unused]] bool sibling) {
     const int cnt = uni(static_cast<int>(s->blk[b].count));
     if (cnt == 0) return 0;
-    const int first = firstLeafOf(static_cast<uint32_t>(b));
-    // One pass packs what the decisions need for every leaf of the block (at most 2 rows):
-    // len | props << kLenBits | removed << 24 | removed at/below minSeq << 25 | insert at/below minSeq << 26
-    // | last UTF-16 unit is '\n' << 27 (TextSegment.canAppend, textSegment.ts:76-93: one LDS read for
-    // all leaves, at their char offsets from a scan of the block's lengths)
-    const int r0 = first >> 6, r1 = (first + cnt - 1) >> 6;
-    Lane<uint32_t> pk0, pk1;
-    Lane<uint32_t> pp0, pp1;  // (large tier: prop-set ids of up to 1024 sets beside the packed words)
-    FOR_LANES(l) {
-      LANE(pk0) = 0u;
-      LANE(pk1) = 0u;
-      LANE(pp0) = 0u;
-      LANE(pp1) = 0u;
-    }
-    uint32_t cs = charOffsetOf(first);  // running char offset of leaf first + k
-    uint32_t rowBase = cs;
-    FOR_ROWS(r, r0, r1 + 1) {
-      Lane<uint32_t> blen;
-      FOR_LANES(l) {
-        const int idx = r * 64 + l;
-        LANE(blen) = idx >= first && idx < first + cnt ? fLen(LANE(W[0])[r]) : 0u;
-      }
-      uint32_t tot;
-      const Lane<uint32_t> ex = waveExclusiveSum(blen, &tot);
-      FOR_LANES(l) {
-        const uint32_t w0 = LANE(W[0])[r];
-        const int32_t ins = static_cast<int32_t>(LANE(W[1])[r]), rm = static_cast<int32_t>(LANE(W[2])[r]);
-        const uint32_t bl = LANE(blen);
-        const bool nl = bl > 0 && chRead(static_cast<int>(rowBase + LANE(ex) + bl - 1)) == 10u;
-        const uint32_t pr = propsL(l, r);
-        bool held = false;  // (Loc) a leaf with pending local ops (zamboni.ts:148)
-        if constexpr (Loc) held = LANE(W[kPendW])[r] != 0u;
-        const uint32_t p = fLen(w0) | ((kPW ? 0u : pr) << C::kLenBits) | (rm != kNotRemoved ? 1u << 24 : 0u) |
-                           (rm <= minSeq ? 1u << 25 : 0u) | (ins <= minSeq ? 1u << 26 : 0u) | (nl ? 1u << 27 : 0u) |
-                           (fMarker(LANE(W[4])[r]) ? 1u << 28 : 0u) | (held ? 1u << 29 : 0u);
-        if (r == r0) LANE(pk0) = p;
-        else LANE(pk1) = p;
-        if constexpr (kPW) {
-          if (r == r0) LANE(pp0) = pr;
-          else LANE(pp1) = pr;
+    int first = -1;
+    uint64_t dropB[2] = {0, 0}, elig[2] = {0, 0};
+    {
+      const int nr = rows();
+      int seen = 0;
+      FOR_ROWS(r, 0, nr) {
+        Lane<bool> inB;
+        FOR_LANES(l) { LANE(inB) = r * 64 + l < n && fBlk(LANE(W[0])[r]) == static_cast<uint32_t>(b); }
+        const uint64_t m = ballot(inB);
+        if (m != 0) {
+          const int k = first < 0 ? 0 : 1;  // leaf blocks are contiguous runs of at most 7 leaves: two rows at most
+          if (first < 0) first = r * 64 + ctz64(m);
+          Lane<bool> dp, ep;
+          FOR_LANES(l) {
+            const int32_t ins = static_cast<int32_t>(LANE(W[1])[r]), rm = static_cast<int32_t>(LANE(W[2])[r]);
+            bool held = false;  // (Loc) a leaf with pending local ops (zamboni.ts:148)
+            if constexpr (Loc) held = LANE(W[kPendW])[r] != 0u;
+            const int idx = r * 64 + l;
+            const bool in = idx >= first && idx < first + cnt;  // (the serial pass's range)
+            LANE(dp) = in && rm != kNotRemoved && rm <= minSeq;
+            LANE(ep) = in && !held && rm == kNotRemoved && ins <= minSeq && !fMarker(LANE(W[4])[r]) &&
+                       fLen(LANE(W[0])[r]) > 0u;
+          }
+          dropB[k] = ballot(dp);
+          elig[k] = ballot(ep);
+          seen += __builtin_popcountll(m);
+          if (k == 1 || seen >= cnt) break;
         }
       }
-      rowBase += tot;
     }
-    stamp(kPfZChars);
-    // serial decisions over <= 7 leaves: keep, merge into the previous kept leaf, or drop
+    const bool pairs = ((elig[0] & (elig[0] << 1)) | (elig[1] & (elig[1] << 1)) | ((elig[0] >> 63) & elig[1])) != 0;
+    const bool drops = (dropB[0] | dropB[1]) != 0;
+    if (!FMT_SCOUR_SLOW && !pairs && !drops) {
+      stamp(kPfZChars);
+      return cnt;
+    }
     uint32_t mergeMask = 0, dropMask = 0;
-    int prev = -1;
-    uint32_t prevLen = 0, prevProps = 0, prevBlk = 0;
-    bool prevNl = false;
     int kept = 0;
-    for (int k = 0; k < cnt; k++) {
-      const int j = first + k;
-      const uint32_t p = (j >> 6) == r0 ? readlane(pk0, j & 63) : readlane(pk1, j & 63);
-      const uint32_t len = p & kLenMask;
-      uint32_t props = (p >> C::kLenBits) & kPropsUndef;
-      if constexpr (kPW) props = (j >> 6) == r0 ? readlane(pp0, j & 63) : readlane(pp1, j & 63);
-      s->tmp[k] = cs;  // char offset and length, for the deletions below
-      s->tmp[kMaxNodes + k] = len;
-      if ((p >> 29) & 1u) {  // held: kept as it is, and nothing appends onto it
-        prev = -1;
-        kept++;
-      } else if (((p >> 24) & 1u) == 0) {
-        if ((p >> 26) & 1u) {
-          const bool lastNl = ((p >> 27) & 1u) != 0;
-          const bool marker = ((p >> 28) & 1u) != 0;  // Marker: never appends, nothing appends onto it
-          const bool canAppend = prev >= 0 && !prevNl && !marker &&
-                                 (prevLen <= static_cast<uint32_t>(kGranularity) ||
-                                  len <= static_cast<uint32_t>(kGranularity)) &&
-                                 propsMatch(prevProps, props) && len > 0;
-          if (canAppend) {
-            mergeMask |= 1u << k;
-            if constexpr (Ob) {  // LocalReferenceCollection.append (localReference.ts:233-251)
-              if (obUsed != 0) obRefsMove(fId(readField(j, 4)), fId(readField(prev, 4)), 0, static_cast<int>(prevLen));
+    uint32_t cs = charOffsetOf(first);  // running char offset of leaf first + k
+    if (!FMT_SCOUR_SLOW && kScourDropOnly && !pairs) {
+      // drops only: their bits from the ballot, and the text spans of the dropped leaves for the move below
+      const int f0 = first & 63;
+      dropMask = static_cast<uint32_t>((dropB[0] >> f0) | ((first >> 6) == ((first + cnt - 1) >> 6) ? 0ull : dropB[1] << (64 - f0))) &
+                 ((1u << cnt) - 1u);
+      kept = cnt - __builtin_popcount(dropMask);
+      for (int k = 0; k < cnt; k++) {
+        const uint32_t len = fLen(readField(first + k, 0));
+        if ((dropMask >> k) & 1u) {
+          s->tmp[k] = cs;
+          s->tmp[kMaxNodes + k] = len;
+        }
+        cs += len;
+      }
+      stamp(kPfZChars);
+    } else {
+      // One pass packs what the decisions need for every leaf of the block (at most 2 rows):
+      // len | props << kLenBits | removed << 24 | removed at/below minSeq << 25 | insert at/below minSeq << 26
+      // | last UTF-16 unit is '\n' << 27 (TextSegment.canAppend, textSegment.ts:76-93: one LDS read for
+      // all leaves, at their char offsets from a scan of the block's lengths)
+      const int r0 = first >> 6, r1 = (first + cnt - 1) >> 6;
+      Lane<uint32_t> pk0, pk1;
+      Lane<uint32_t> pp0, pp1;  // (large tier: prop-set ids of up to 1024 sets beside the packed words)
+      FOR_LANES(l) {
+        LANE(pk0) = 0u;
+        LANE(pk1) = 0u;
+        LANE(pp0) = 0u;
+        LANE(pp1) = 0u;
+      }
+      uint32_t rowBase = cs;
+      FOR_ROWS(r, r0, r1 + 1) {
+        Lane<uint32_t> blen;
+        FOR_LANES(l) {
+          const int idx = r * 64 + l;
+          LANE(blen) = idx >= first && idx < first + cnt ? fLen(LANE(W[0])[r]) : 0u;
+        }
+        uint32_t tot;
+        const Lane<uint32_t> ex = waveExclusiveSum(blen, &tot);
+        FOR_LANES(l) {
+          const uint32_t w0 = LANE(W[0])[r];
+          const int32_t ins = static_cast<int32_t>(LANE(W[1])[r]), rm = static_cast<int32_t>(LANE(W[2])[r]);
+          const uint32_t bl = LANE(blen);
+          const bool nl = bl > 0 && chRead(static_cast<int>(rowBase + LANE(ex) + bl - 1)) == 10u;
+          const uint32_t pr = propsL(l, r);
+          bool held = false;  // (Loc) a leaf with pending local ops (zamboni.ts:148)
+          if constexpr (Loc) held = LANE(W[kPendW])[r] != 0u;
+          const uint32_t p = fLen(w0) | ((kPW ? 0u : pr) << C::kLenBits) | (rm != kNotRemoved ? 1u << 24 : 0u) |
+                             (rm <= minSeq ? 1u << 25 : 0u) | (ins <= minSeq ? 1u << 26 : 0u) | (nl ? 1u << 27 : 0u) |
+                             (fMarker(LANE(W[4])[r]) ? 1u << 28 : 0u) | (held ? 1u << 29 : 0u);
+          if (r == r0) LANE(pk0) = p;
+          else LANE(pk1) = p;
+          if constexpr (kPW) {
+            if (r == r0) LANE(pp0) = pr;
+            else LANE(pp1) = pr;
+          }
+        }
+        rowBase += tot;
+      }
+      stamp(kPfZChars);
+      // serial decisions over <= 7 leaves: keep, merge into the previous kept leaf, or drop
+      int prev = -1;
+      uint32_t prevLen = 0, prevProps = 0, prevBlk = 0;
+      bool prevNl = false;
+      for (int k = 0; k < cnt; k++) {
+        const int j = first + k;
+        const uint32_t p = (j >> 6) == r0 ? readlane(pk0, j & 63) : readlane(pk1, j & 63);
+        const uint32_t len = p & kLenMask;
+        uint32_t props = (p >> C::kLenBits) & kPropsUndef;
+        if constexpr (kPW) props = (j >> 6) == r0 ? readlane(pp0, j & 63) : readlane(pp1, j & 63);
+        s->tmp[k] = cs;  // char offset and length, for the deletions below
+        s->tmp[kMaxNodes + k] = len;
+        if ((p >> 29) & 1u) {  // held: kept as it is, and nothing appends onto it
+          prev = -1;
+          kept++;
+        } else if (((p >> 24) & 1u) == 0) {
+          if ((p >> 26) & 1u) {
+            const bool lastNl = ((p >> 27) & 1u) != 0;
+            const bool marker = ((p >> 28) & 1u) != 0;  // Marker: never appends, nothing appends onto it
+            const bool canAppend = prev >= 0 && !prevNl && !marker &&
+                                   (prevLen <= static_cast<uint32_t>(kGranularity) ||
+                                    len <= static_cast<uint32_t>(kGranularity)) &&
+                                   propsMatch(prevProps, props) && len > 0;
+            if (canAppend) {
+              mergeMask |= 1u << k;
+              if constexpr (Ob) {  // LocalReferenceCollection.append (localReference.ts:233-251)
+                if (obUsed != 0) obRefsMove(fId(readField(j, 4)), fId(readField(prev, 4)), 0, static_cast<int>(prevLen));
+              }
+              prevLen += len;
+              prevNl = lastNl;
+              // the head keeps its index until the deletions below, so its length can be set now
+              writeField(prev, 0, mkW0(prevLen, prevBlk, prevProps));
+            } else {
+              prev = len > 0 && !marker ? j : -1;
+              prevLen = len;
+              prevProps = props;
+              prevBlk = static_cast<uint32_t>(b);
+              prevNl = lastNl;
+              kept++;
             }
-            prevLen += len;
-            prevNl = lastNl;
-            // the head keeps its index until the deletions below, so its length can be set now
-            writeField(prev, 0, mkW0(prevLen, prevBlk, prevProps));
           } else {
-            prev = len > 0 && !marker ? j : -1;
-            prevLen = len;
-            prevProps = props;
-            prevBlk = static_cast<uint32_t>(b);
-            prevNl = lastNl;
+            prev = -1;
             kept++;
           }
         } else {
+          if ((p >> 25) & 1u) {
+            dropMask |= 1u << k;
+          } else {
+            kept++;
+          }
           prev = -1;
-          kept++;
         }
-      } else {
-        if ((p >> 25) & 1u) {
-          dropMask |= 1u << k;
-        } else {
-          kept++;
-        }
-        prev = -1;
+        cs += len;
       }
-      cs += len;
     }
     waveSync();
     stamp(kPfZSerial);
@@ -3545,6 +3618,7 @@ class Doc {
     if constexpr (Adj || Loc) {  // appended and unlinked leaves take their managers with them
       for (uint32_t m = pmN > 0 ? (mergeMask | dropMask) : 0u; m != 0; m &= m - 1) pmDropLeaf(fId(readField(first + ctz32(m), 4)));
     }
+    FMT_SCOUR_NOTE(sibling, pairs, drops, mergeMask, dropMask);
     deleteLeaves(first, cnt, mergeMask | dropMask);
     stamp(kPfZDelete);
     return kept;
@@ -3613,7 +3687,7 @@ class Doc {
       const int oldCount = uni(static_cast<int>(s->blk[b].count));
       int target = b, p = -1, ci = 0, total = 0, firstLeaf = -1;
       for (;;) {
-        const int kept = scourLeafBlock(target);
+        const int kept = scourLeafBlock(target, p >= 0);
         if (status != FMT_OK) return;
         if (p < 0) {  // the popped block itself
           s->blk[b].needsScour = 0;

@@ -138,6 +138,15 @@ struct LargeTier {
   for (int r = kRowUnroll > 1 ? kRows - 1 : ((hi) < kRows ? (hi) : kRows) - 1; r >= (kRowUnroll > 1 ? 0 : (lo)); r--) \
     if (r >= (lo) && r < (hi))
 
+template <class A, class B>
+struct SameTier {
+  static constexpr bool value = false;
+};
+template <class A>
+struct SameTier<A, A> {
+  static constexpr bool value = true;
+};
+
 template <class BId>
 struct Blk {
   uint8_t count;
@@ -285,11 +294,20 @@ struct DocOutputs {
 // scour takes the serial pass and reports what its ballots predicted beside what the pass found.
 #if !FMT_GPU && defined(FMT_SCOUR_COUNT)
 extern "C" void fmtScourNote(int sibling, int pairs, int drops, uint32_t mergeMask, uint32_t dropMask);
+// per packParent: its start (children, leaves in the span), each sibling's text move (units moved), its end
+// (units one move over the whole span would have taken)
+extern "C" void fmtPackNote(int what, int a, int b);
 #define FMT_SCOUR_SLOW 1
 #define FMT_SCOUR_NOTE(sibling, pairs, drops, mergeMask, dropMask) fmtScourNote(sibling, pairs, drops, mergeMask, dropMask)
+#define FMT_PACK_NOTE(what, a, b) fmtPackNote(what, a, b)
 #else
 #define FMT_SCOUR_SLOW 0
 #define FMT_SCOUR_NOTE(sibling, pairs, drops, mergeMask, dropMask) ((void)0)
+#define FMT_PACK_NOTE(what, a, b) ((void)0)
+#endif
+// A/B switch: the plain compact kernel with packParent's span scour (see Doc::kSpanScour).
+#ifndef FMT_SPAN_COMPACT
+#define FMT_SPAN_COMPACT 0
 #endif
 enum ProfCat {
   kPfOpLoad, kPfScan, kPfSplit, kPfInsert, kPfRange, kPfLru, kPfZamboniOp, kPfWindow, kPfOutput,
@@ -3593,6 +3611,7 @@ class Doc {
       for (int k = 0; k < cnt; k++)
         if ((dropMask >> k) & 1u) dropped += uni(s->tmp[kMaxNodes + k]);
       const int newChars = nChars - static_cast<int>(dropped);
+      if (sibling) FMT_PACK_NOTE(1, static_cast<int>(c0), newChars);
       for (int base = static_cast<int>(c0); base < newChars; base += 64) {
         Lane<uint32_t> v;
         FOR_LANES(l) {
@@ -3622,6 +3641,255 @@ class Doc {
     deleteLeaves(first, cnt, mergeMask | dropMask);
     stamp(kPfZDelete);
     return kept;
+  }
+
+  // packParent's scour of every child of p in one pass (DESIGN.md §4.1 "packParent: one scour for the
+  // span"). The children's leaves are one contiguous run of at most 7 x 7 leaves in at most two rows, so
+  // one 64-bit mask indexed from the span's first leaf holds a bit per leaf. The decisions are
+  // scourLeafBlock's, block by block (`starts` marks each block's first leaf: nothing is appended across
+  // it); the text is moved once and the leaf registers are compacted once. Returns the leaves left, which
+  // start at *firstLeaf.
+  // The plain compact kernel keeps the per-child loop: it sits at its 128-register limit (4 waves/SIMD) and
+  // the span scour costs it five more spilled VGPRs, 20 B/lane of scratch (-DFMT_SPAN_COMPACT=1
+  // builds it with the span scour for an A/B). The counting build keeps the loop in every tier.
+  static constexpr bool kPlainCompact = SameTier<C, CompactTier>::value && !Ob && !Loc;
+  static constexpr bool kSpanScour = !FMT_SCOUR_SLOW && (FMT_SPAN_COMPACT || !kPlainCompact);
+
+  // Bits of two row ballots from lane f0 of the first row on.
+  FMT_DEV static uint64_t spanBits(uint64_t b0, uint64_t b1, int f0) {
+    return f0 == 0 ? b0 : (b0 >> f0) | (b1 << (64 - f0));
+  }
+
+  // Position of the n-th (from 0) set bit of m, n < popcount(m); per lane.
+  FMT_DEV static int nthSetBit(uint64_t m, int n) {
+    int pos = 0;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+      const int c = __builtin_popcountll(m & ((1ull << w) - 1ull));
+      if (n >= c) {
+        n -= c;
+        m >>= w;
+        pos += w;
+      }
+    }
+    return pos;
+  }
+
+  // deleteLeaves for a span: bit k of `dead` deletes leaf first + k, k < cnt <= 49. Slot i of the kept span
+  // takes the (i - first)-th surviving leaf, every later slot leaf i + d: the same row or the next.
+  FMT_DEV void deleteSpanLeaves(int first, int cnt, uint64_t dead) {
+    const int d = __builtin_popcountll(dead);
+    if (d == 0) return;
+    const uint64_t alive = ~dead & (cnt >= 64 ? ~0ull : (1ull << cnt) - 1ull);
+    const int nr = rows(), nNew = n - d, keptEnd = first + cnt - d;
+    FOR_ROWS(r, first >> 6, nr) {
+      Lane<int> src;
+      Lane<bool> fromNext, live;
+      FOR_LANES(l) {
+        const int i = r * 64 + l;
+        int from = i + d;
+        if (i < first) from = i;
+        else if (i < keptEnd) from = first + nthSetBit(alive, i - first);
+        LANE(src) = from & 63;
+        LANE(fromNext) = (from >> 6) > r;
+        LANE(live) = i < nNew;
+      }
+#pragma unroll
+      for (int f = 0; f < kWords; f++) {
+        const Lane<uint32_t> a = gather(row(W[f], r), src);
+        const Lane<uint32_t> b = gather(row(W[f], r + 1 < kRows ? r + 1 : r), src);
+        FOR_LANES(l) { LANE(W[f])[r] = LANE(live) ? (LANE(fromNext) && r + 1 < kRows ? LANE(b) : LANE(a)) : 0u; }
+      }
+    }
+    n = nNew;
+  }
+
+  FMT_DEV int scourSpan(int p, int* firstLeaf) {
+    const int pc = uni(static_cast<int>(s->blk[p].count));
+    int cnt = 0, firstChild = -1;
+    uint64_t starts = 0;  // bit k: leaf first + k is the first of its block
+    for (int q = 0; q < pc; q++) {
+      const int c = uni(static_cast<int>(s->blk[p].child[q]));
+      const int cc = uni(static_cast<int>(s->blk[c].count));
+      if (cc == 0) continue;
+      if (firstChild < 0) firstChild = c;
+      starts |= 1ull << cnt;
+      cnt += cc;
+    }
+    *firstLeaf = -1;
+    if (cnt == 0) return 0;
+    const int first = firstLeafOf(static_cast<uint32_t>(firstChild));
+    *firstLeaf = first;
+    const int r0 = first >> 6, r1 = (first + cnt - 1) >> 6, f0 = first & 63;
+    // the ballots of scourLeafBlock over the span's rows (a held leaf is never dropped: the serial pass's order)
+    uint64_t d0 = 0, d1 = 0, e0 = 0, e1 = 0;
+    FOR_ROWS(r, r0, r1 + 1) {
+      Lane<bool> dp, ep;
+      FOR_LANES(l) {
+        const int32_t ins = static_cast<int32_t>(LANE(W[1])[r]), rm = static_cast<int32_t>(LANE(W[2])[r]);
+        bool held = false;
+        if constexpr (Loc) held = LANE(W[kPendW])[r] != 0u;
+        const int idx = r * 64 + l;
+        const bool in = idx >= first && idx < first + cnt;
+        LANE(dp) = in && !held && rm != kNotRemoved && rm <= minSeq;
+        LANE(ep) = in && !held && rm == kNotRemoved && ins <= minSeq && !fMarker(LANE(W[4])[r]) && fLen(LANE(W[0])[r]) > 0u;
+      }
+      if (r == r0) {
+        d0 = ballot(dp);
+        e0 = ballot(ep);
+      } else {
+        d1 = ballot(dp);
+        e1 = ballot(ep);
+      }
+    }
+    const uint64_t drop = spanBits(d0, d1, f0), elig = spanBits(e0, e1, f0);
+    const uint64_t pairs = elig & (elig << 1) & ~starts;  // leaf k and leaf k - 1 of its own block both in E
+    stamp(kPfZFind);  // (scourLeafBlock counts its find pass and ballots as z_chars)
+    if (pairs == 0 && drop == 0) {
+      stamp(kPfZChars);
+      return cnt;
+    }
+    // with pairs: whether an E leaf ends in '\n' (TextSegment.canAppend), one text read at the char offsets from
+    // a scan of the span's lengths
+    const uint32_t cs = charOffsetOf(first);
+    uint64_t n0 = 0, n1 = 0;
+    if (pairs != 0) {
+      uint32_t rowBase = cs;
+      FOR_ROWS(r, r0, r1 + 1) {
+        const uint64_t eRow = r == r0 ? e0 : e1;
+        Lane<uint32_t> blen;
+        FOR_LANES(l) {
+          const int idx = r * 64 + l;
+          LANE(blen) = idx >= first && idx < first + cnt ? fLen(LANE(W[0])[r]) : 0u;
+        }
+        uint32_t tot;
+        const Lane<uint32_t> ex = waveExclusiveSum(blen, &tot);
+        Lane<bool> nl;
+        FOR_LANES(l) {
+          LANE(nl) = ((eRow >> l) & 1ull) != 0 && chRead(static_cast<int>(rowBase + LANE(ex) + LANE(blen) - 1)) == 10u;
+        }
+        if (r == r0) n0 = ballot(nl);
+        else n1 = ballot(nl);
+        rowBase += tot;
+      }
+    }
+    stamp(kPfZChars);
+    // The serial decisions, over the leaves that can append or be appended onto: a leaf outside E ends a
+    // run, and so does a block's first leaf.
+    uint64_t mergeMask = 0;
+    if (pairs != 0) {
+      const uint64_t nls = spanBits(n0, n1, f0);
+      const Lane<uint32_t> a0 = selectRow(W[0], r0), a1 = selectRow(W[0], r1);
+      Lane<uint32_t> q0, q1;
+      if constexpr (kPW) {
+        q0 = selectRow(W[kPropW], r0);
+        q1 = selectRow(W[kPropW], r1);
+      }
+      int prev = -1;
+      uint32_t prevLen = 0, prevProps = 0, prevW0 = 0;
+      bool prevNl = false;
+      for (uint64_t m = pairs | (pairs >> 1); m != 0; m &= m - 1) {
+        const int k = ctz64(m), j = first + k;
+        const bool lo = (j >> 6) == r0;
+        const uint32_t w0 = lo ? readlane(a0, j & 63) : readlane(a1, j & 63);
+        const uint32_t len = fLen(w0);
+        uint32_t props = fProps(w0);
+        if constexpr (kPW) props = lo ? readlane(q0, j & 63) : readlane(q1, j & 63);
+        const bool lastNl = ((nls >> k) & 1ull) != 0;
+        if (((pairs >> k) & 1ull) == 0) prev = -1;
+        const bool canAppend = prev >= 0 && !prevNl &&
+                               (prevLen <= static_cast<uint32_t>(kGranularity) || len <= static_cast<uint32_t>(kGranularity)) &&
+                               propsMatch(prevProps, props);
+        if (canAppend) {
+          mergeMask |= 1ull << k;
+          if constexpr (Ob) {  // LocalReferenceCollection.append (localReference.ts:233-251)
+            if (obUsed != 0) obRefsMove(fId(readField(j, 4)), fId(readField(prev, 4)), 0, static_cast<int>(prevLen));
+          }
+          prevLen += len;
+          prevNl = lastNl;
+          // the head keeps its index until the deletions below, so its length can be set now
+          writeField(prev, 0, (prevW0 & ~kLenMask) | prevLen);
+        } else {
+          prev = j;
+          prevLen = len;
+          prevProps = props;
+          prevW0 = w0;
+          prevNl = lastNl;
+        }
+      }
+    }
+    stamp(kPfZSerial);
+    // One text move: every unit behind the first dropped leaf goes down by the dropped lengths before it.
+    if (drop != 0) {
+      // for each dropped leaf: the first text unit (after the move) that lies behind it, and the dropped
+      // lengths up to and with it. Merged heads have their new lengths by now, appended leaves still their
+      // own, so the offsets are those of the text as it lies.
+      Lane<uint32_t> thr0, thr1, cum0, cum1;
+      {
+        uint32_t rowBase = cs, dropBase = 0;
+        FOR_ROWS(r, r0, r1 + 1) {
+          const uint64_t dRow = r == r0 ? d0 : d1, mRow = r == r0 ? mergeMask << f0 : (f0 == 0 ? 0ull : mergeMask >> (64 - f0));
+          Lane<uint32_t> blen, dlen;
+          FOR_LANES(l) {
+            const int idx = r * 64 + l;
+            // (an appended leaf's units are counted in its head's new length)
+            LANE(blen) = idx >= first && idx < first + cnt && ((mRow >> l) & 1ull) == 0 ? fLen(LANE(W[0])[r]) : 0u;
+            LANE(dlen) = (dRow >> l) & 1ull ? LANE(blen) : 0u;
+          }
+          uint32_t tot, dtot;
+          const Lane<uint32_t> ex = waveExclusiveSum(blen, &tot);
+          const Lane<uint32_t> dex = waveExclusiveSum(dlen, &dtot);
+          FOR_LANES(l) {
+            const uint32_t before = dropBase + LANE(dex);
+            const uint32_t t = rowBase + LANE(ex) - before, u = before + LANE(blen);
+            if (r == r0) {
+              LANE(thr0) = t;
+              LANE(cum0) = u;
+            } else {
+              LANE(thr1) = t;
+              LANE(cum1) = u;
+            }
+          }
+          rowBase += tot;
+          dropBase += dtot;
+        }
+      }
+      const int kf = first + ctz64(drop), kl = first + 63 - __builtin_clzll(drop);
+      const uint32_t c0 = (kf >> 6) == r0 ? readlane(thr0, kf & 63) : readlane(thr1, kf & 63);
+      const uint32_t dropped = (kl >> 6) == r0 ? readlane(cum0, kl & 63) : readlane(cum1, kl & 63);
+      const int newChars = nChars - static_cast<int>(dropped);
+      for (int base = static_cast<int>(c0); base < newChars; base += 64) {
+        Lane<uint32_t> shift;
+        FOR_LANES(l) { LANE(shift) = 0u; }
+        for (uint64_t m = drop; m != 0; m &= m - 1) {
+          const int j = first + ctz64(m);
+          const uint32_t t = (j >> 6) == r0 ? readlane(thr0, j & 63) : readlane(thr1, j & 63);
+          if (t > static_cast<uint32_t>(base + 63)) break;  // (ascending: no later one reaches this chunk)
+          const uint32_t u = (j >> 6) == r0 ? readlane(cum0, j & 63) : readlane(cum1, j & 63);
+          FOR_LANES(l) {
+            if (static_cast<uint32_t>(base + l) >= t) LANE(shift) = u;
+          }
+        }
+        Lane<uint32_t> v;
+        FOR_LANES(l) {
+          const int c = base + l;
+          LANE(v) = c < newChars ? chRead(c + static_cast<int>(LANE(shift))) : 0u;
+        }
+        waveSync();
+        FOR_LANES(l) {
+          if (base + l < newChars) chWrite(base + l, LANE(v));
+        }
+        waveSync();
+      }
+      nChars = newChars;
+    }
+    const uint64_t dead = mergeMask | drop;
+    if constexpr (Adj || Loc) {  // appended and unlinked leaves take their managers with them
+      for (uint64_t m = pmN > 0 ? dead : 0ull; m != 0; m &= m - 1) pmDropLeaf(fId(readField(first + ctz64(m), 4)));
+    }
+    deleteSpanLeaves(first, cnt, dead);
+    stamp(kPfZDelete);
+    return cnt - __builtin_popcountll(dead);
   }
 
   // packParent redistribution (zamboni.ts:83-139) of `total` held children into
@@ -3698,18 +3966,30 @@ class Doc {
           const int parent = uni(static_cast<int>(s->blk[b].parent));
           if (kept >= kMaxNodes / 2 || parent == static_cast<int>(kNoBlk)) break;
           p = parent;  // packParent(parent): scour every child block of p, in order
-          ci = 0;
-          target = uni(static_cast<int>(s->blk[p].child[0]));
-          continue;
+          if constexpr (kSpanScour) {
+            total = scourSpan(p, &firstLeaf);
+          } else {
+            ci = 0;
+#if FMT_SCOUR_SLOW
+            int leaves = 0;
+            const int pc = static_cast<int>(s->blk[p].count);
+            for (int q = 0; q < pc; q++) leaves += static_cast<int>(s->blk[s->blk[p].child[q]].count);
+            FMT_PACK_NOTE(0, pc, leaves);
+#endif
+            target = uni(static_cast<int>(s->blk[p].child[0]));
+            continue;
+          }
+        } else {  // a sibling, child by child (the plain compact kernel and the counting build)
+          s->blk[target].count = static_cast<uint8_t>(kept);
+          waveSync();
+          if (kept > 0 && firstLeaf < 0) firstLeaf = firstLeafOf(static_cast<uint32_t>(target));
+          total += kept;
+          if (++ci < uni(static_cast<int>(s->blk[p].count))) {
+            target = uni(static_cast<int>(s->blk[p].child[ci]));
+            continue;
+          }
         }
-        s->blk[target].count = static_cast<uint8_t>(kept);
-        waveSync();
-        if (kept > 0 && firstLeaf < 0) firstLeaf = firstLeafOf(static_cast<uint32_t>(target));
-        total += kept;
-        if (++ci < uni(static_cast<int>(s->blk[p].count))) {
-          target = uni(static_cast<int>(s->blk[p].child[ci]));
-          continue;
-        }
+        FMT_PACK_NOTE(2, nChars, total);
         redistribute(p, total, true, firstLeaf);
         if (status != FMT_OK) return;
         // interior levels: scourNode holds block children as they are
